@@ -16,6 +16,12 @@ per step on the library's stream (gaml_hip_comm_init_rank; the id travels over t
 (833,333 fresh pairs per GPU) and the other exchanges (GAML_BENCH_EXCHANGE=rccl-torch|shm) are explicitly labelled
 alternatives.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) is the headline alone: set-up, priming, warm-up, the K timed
+steps, the result line. `--full` adds everything else the line can carry (the kernel-timing pass and `roofline`, the
+CPU baselines, the batched / annealing / aligner / repeat-rich / jumping-library / drift blocks; N > 1: the check
+against N = 1, the in-process multi-device run, weak scaling); the `--no-*` switches thin a `--full` run out.
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as float64 .npy files.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -77,6 +83,24 @@ def path_variants(walk, k=8):
         cut = max(1, min(n - 1, cut))
         out.append([list(walk[:cut]), list(walk[cut:])])
     return out
+
+
+DUMP_MAX_VALUES = 3 << 20  # 24 MB of float64 per array: a larger output goes out as a fixed, seeded sample + its index
+
+
+def dump_outputs(out_dir, ctx, rs, value):
+    """What the last timed step gave its caller -- CalcProb's value, floored reads per read set (zeros) and total_len --
+    and the per-read probabilities it left in the read set, as float64 .npy files in `out_dir`. Called right after the
+    timed region, before anything else scores on the context."""
+    os.makedirs(out_dir, exist_ok=True)
+    probs = ctx.read_probs(rs)
+    arrays = {"log_likelihood": np.array([value]), "floored_reads": ctx.last_zeros,
+              "total_len": np.array([ctx.last_total_len]), "read_probs": probs}
+    if probs.size > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.default_rng(0).choice(probs.size, DUMP_MAX_VALUES, replace=False))
+        arrays["read_probs"], arrays["read_probs_index"] = probs[idx], idx
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(gb, go, b1, o1, b2, o2, pairs, read_len, variants, cfg, budget_s=10.0):
@@ -687,11 +711,18 @@ def main():
     ap.add_argument("--cpu-shard-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-shard-budget", type=float, default=8.0, help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu-sharded", action="store_true", help="skip the N-process CPU courtesy row")
+    ap.add_argument("--full", action="store_true", help="besides the headline: kernel-timing pass (roofline), CPU baselines and "
+                    "every untimed block; without it a run is set-up, warm-up, the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (log-likelihood, floored reads, total length, per-read "
+                         "probabilities) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.inproc_devices:
         return inproc_child(args)
     if args.cpu_shard_child:
         return cpu_shard_child(args)
+    if not args.full:  # a plain run: what the headline needs, nothing else
+        args.no_extras = args.no_cpu_baseline = args.no_inproc = True
 
     import torch
     import torch.distributed as dist
@@ -840,6 +871,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share_gpu else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, rs, last)
 
     # ---- separate pass: HIP events attached to EVERY scoring dispatch (not part of the throughput number)
     ks = {"launches": 0, "device_us": 0.0, "algo_bytes": 0.0}
@@ -920,26 +953,36 @@ def main():
         total_reads = 2.0 * total_pairs
         ms_per_step = 1e3 * elapsed / args.steps
         value = total_reads * args.steps / elapsed
-        launches = max(1, ks["launches"])
-        kern_us = ks["device_us"] / launches
-        bytes_per_launch = ks["algo_bytes"] / launches
-        achieved = bytes_per_launch / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
-        # HBM traffic per launch comes from rocprofv3 --pmc passes of this same command (counters cannot be read from
-        # inside the process): only a profile taken on THESE sources counts, otherwise null + traffic_stale
-        traffic, traffic_src, traffic_stale = None, None, None
-        try:
-            import glob
-            # (the newest summary taken for THIS workload: <tag>_pmc_traffic.json is cfg3's, <tag>_cfg3x8_pmc_traffic.json the HBM-bound size's)
-            cands = [f for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "*pmc_traffic.json")))
-                     if json.load(open(f)).get("workload", "cfg3") == args.workload]
-            f = cands[-1]
-            tj = json.load(open(f))
-            traffic_src = os.path.relpath(f, ROOT)
-            traffic_stale = tj.get("source_hash") != source_hash()
-            if world == 1 and not traffic_stale:
-                traffic = tj["kernels"]["paired_score_kernel"]["hbm_bytes_per_launch"]
-        except Exception:
-            pass
+        roofline = None  # (--full: from the kernel-timing pass)
+        if args.full:
+            launches = max(1, ks["launches"])
+            kern_us = ks["device_us"] / launches
+            bytes_per_launch = ks["algo_bytes"] / launches
+            achieved = bytes_per_launch / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
+            # HBM traffic per launch comes from rocprofv3 --pmc passes of this same command (counters cannot be read from
+            # inside the process): only a profile taken on THESE sources counts, otherwise null + traffic_stale
+            traffic, traffic_src, traffic_stale = None, None, None
+            try:
+                import glob
+                # (the newest summary taken for THIS workload: <tag>_pmc_traffic.json is cfg3's, <tag>_cfg3x8_pmc_traffic.json the HBM-bound size's)
+                cands = [f for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "*pmc_traffic.json")))
+                         if json.load(open(f)).get("workload", "cfg3") == args.workload]
+                f = cands[-1]
+                tj = json.load(open(f))
+                traffic_src = os.path.relpath(f, ROOT)
+                traffic_stale = tj.get("source_hash") != source_hash()
+                if world == 1 and not traffic_stale:
+                    traffic = tj["kernels"]["paired_score_kernel"]["hbm_bytes_per_launch"]
+            except Exception:
+                pass
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                        "kernel": "paired_score_kernel", "kernel_us": kern_us, "algo_bytes_per_launch": bytes_per_launch,
+                        "timing": "HIP events attached to the dispatch (hipExtLaunchKernelGGL, on the launch stream) of EVERY "
+                                  "paired_score_kernel launch of a separate pass after the timed region: the kernel's own begin/end "
+                                  "stamps, as in rocprofv3's kernel trace",
+                        "timed_launches": int(launches), "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+                        "source_hash": source_hash()}
         d = np.diff(stamps) * 1e6
         out = {
             "metric": "reads_per_sec_scored", "value": value, "unit": "reads/s", "n_gpus": world,
@@ -956,14 +999,7 @@ def main():
             "exchange": exchange, "rccl_ranks": world if exchange in ("rccl", "rccl-torch") else 0,
             "exchange_form": (ctx.exchange() if exchange == "rccl" else None), "comm_setup_s": comm_setup_s,
             "ll_rel_delta_vs_n1": ll_delta_n1,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": "paired_score_kernel", "kernel_us": kern_us, "algo_bytes_per_launch": bytes_per_launch,
-                         "timing": "HIP events attached to the dispatch (hipExtLaunchKernelGGL, on the launch stream) of EVERY "
-                                   "paired_score_kernel launch of a separate pass after the timed region: the kernel's own begin/end "
-                                   "stamps, as in rocprofv3's kernel trace",
-                         "timed_launches": int(launches), "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                         "source_hash": source_hash()},
+            "roofline": roofline,
             "step_us_distribution": {"p50": float(np.percentile(d, 50)), "p90": float(np.percentile(d, 90)),
                                      "p99": float(np.percentile(d, 99)), "max": float(d.max())},
             "log_likelihood": last, "prime_s": prime_s,

@@ -5,6 +5,7 @@ Two kinds of fixture, kept apart on purpose:
   * ref_*.json    -- produced by the REFERENCE's own code: oracle/_ref/libref_logdouble.so is our
                      driver TU compiled against /root/reference/logdouble.hpp and utility.h in place
                      (the only reference files that build without Boost). These pin the oracle.
+                     ref_logdouble_live.npz holds its answers on the random operands of the live-library test.
   * oracle_*.json -- produced by OUR oracle (oracle/gaml_oracle.cc) on seeded synthetic inputs.
                      They are regression pins for the oracle and the product, NOT reference
                      output: graph.cc cannot be built here (Boost absent, stand-ins not allowed) and
@@ -58,6 +59,20 @@ def ref_logdouble():
         inv.append({"walk": w, "invert": [int(x) for x in out[:n]], "reverse": [int(x) for x in rev[:len(w)]]})
     return {"source": "reference logdouble.hpp + utility.h compiled in place (oracle/_ref)", "default": hexf(R.ref_ld_default()),
             "binary": rows, "ctor": ctor, "pow": pows, "paths": inv}
+
+
+def ref_logdouble_live():
+    """The reference's answers on the random operands of tests/test_oracle_ref.py::test_live_reference_library_if_present
+    (same seed, same draws), so that the test checks the oracle against them where oracle/_ref is not built."""
+    R = op.ref_lib()
+    assert R is not None, "oracle/_ref/libref_logdouble.so missing: run make -C oracle with the reference tree present"
+    rng = np.random.default_rng(0)
+    vals = list(rng.uniform(-800, 5, 400)) + [-math.inf, 0.0]
+    xs = rng.uniform(0, 2, 100)
+    a, b = np.array(vals[:60]), np.array(vals[-60:])
+    return {"a": a, "b": b, "add": np.array([[R.ref_ld_add(x, y) for y in b] for x in a]),
+            "mul": np.array([[R.ref_ld_mul(x, y) for y in b] for x in a]),
+            "x": xs, "from_linear": np.array([R.ref_ld_from_linear(x) for x in xs])}
 
 
 def tiny_case(seed=5, G=30_000, n=1500, penalty=0.0):
@@ -215,9 +230,12 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "sam":  # only the PacBio SAM pins (the other fixtures stay as they are)
         with open(os.path.join(HERE, "pacbio_sam_pins.json"), "w") as f:
             json.dump(pacbio_sam_pins(), f, indent=0)
+    elif len(sys.argv) > 1 and sys.argv[1] == "live":  # only the stored answers of the live-library test
+        np.savez(os.path.join(HERE, "ref_logdouble_live.npz"), **ref_logdouble_live())
     else:
         with open(os.path.join(HERE, "ref_logdouble.json"), "w") as f:
             json.dump(ref_logdouble(), f, indent=0)
+        np.savez(os.path.join(HERE, "ref_logdouble_live.npz"), **ref_logdouble_live())
         with open(os.path.join(HERE, "oracle_pins.json"), "w") as f:
             json.dump(oracle_pins(), f, indent=0)
         with open(os.path.join(HERE, "pacbio_sam_pins.json"), "w") as f:
