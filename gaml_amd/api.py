@@ -212,6 +212,10 @@ def _load():
         L.gaml_hip_debug_static_check.argtypes = [vp, C.c_int, _i64p]
     if hasattr(L, "gaml_hip_debug_set_knob"):  # development build only
         L.gaml_hip_debug_set_knob.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "gaml_hip_debug_occ_route"):  # development build only
+        L.gaml_hip_debug_occ_route.argtypes = [vp, C.c_int, _i64p]
+    if hasattr(L, "gaml_hip_debug_occ_check"):  # development build only
+        L.gaml_hip_debug_occ_check.argtypes = [vp, C.c_int, _i64p]
     if hasattr(L, "gaml_hip_shm_exchange_open"):
         L.gaml_hip_shm_exchange_open.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
         L.gaml_hip_shm_allreduce_sum.argtypes = [vp, C.c_void_p, C.c_int32]
@@ -740,6 +744,24 @@ class Context:
         self._check(_lib.gaml_hip_debug_static_check(self._h, rs, out))
         return {"static_pairs": int(out[0]), "other_pairs": int(out[1]), "violations": int(out[2]), "no_record": int(out[3]),
                 "different_windows": int(out[4]), "orientation": int(out[5]), "distance": int(out[6]), "edits_or_code": int(out[7])}
+
+    def debug_occ_route(self, rs):
+        """Whole-set calls whose occurrence tables the device built / the host built / that were evaluated again on the
+        host route (two paths share a window), pool compactions, pool entries in use (development build)."""
+        out = np.zeros(6, np.int64)
+        self._check(_lib.gaml_hip_debug_occ_route(self._h, rs, out))
+        return {"device": int(out[0]), "host": int(out[1]), "fallbacks": int(out[2]), "compactions": int(out[3]),
+                "pool_entries": int(out[4]), "shared_combinations": int(out[5])}
+
+    def debug_occ_check(self, rs):
+        """After a call on the device route: its device tables against the host image of the same set, entry by entry
+        (development build). All zeros when the last call did not take the route."""
+        out = np.zeros(4, np.int64)
+        rc = _lib.gaml_hip_debug_occ_check(self._h, rs, out)
+        res = {"compared": int(out[0]), "present": int(out[1]), "mismatches": int(out[2]), "lists": int(out[3])}
+        if rc != 0 and res["compared"] == 0:
+            self._check(rc)
+        return res
 
     def debug_tables_check(self, rs):
         """The device table build against the host restatement, entry by entry (development build)."""

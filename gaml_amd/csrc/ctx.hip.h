@@ -307,6 +307,36 @@ struct PairedSet {
     bool valid = false;                // the copy mirrors the host images as of their last take_changed()
     void release() { if (dev) (void)hipFree(dev); dev = nullptr; bytes = 0; valid = false; }
   } persist;
+  // Whole-set blocking calls on the resident route build the occurrence tables on the device (occ_device.hip.h): every
+  // memo's prepacked entries (PathMemo::pre) stay in a pool in device memory, a call sends one descriptor per path and
+  // occ_scatter_kernel writes the entries into one of two tables per mate (used in alternation; the other one is cleared
+  // in the same launch). The host images are not built for such a call: they go stale until a consumer rebuilds them.
+  struct OccDev {
+    DevBuf pool[2];                    // OccPre ranges, one per memo and mate, bump-allocated; compacted when full
+    size_t pool_cap[2] = {0, 0}, pool_used[2] = {0, 0};
+    uint32_t pool_gen = 1;             // a memo's range is valid while PathMemo::dev_gen equals this
+    PinBuf stage;                      // uploads of new ranges: staged here, copied in stream order
+    DevBuf tab[2][2], list[2][2];      // [mate][table]: 12-byte entries (all ones: absent) / window ids the table last received
+    DevBuf stamp[2];                   // per window: serial of the last call that wrote it (duplicates between paths)
+    size_t cap_w = 0, cap_list = 0;
+    int32_t list_n[2][2] = {{0, 0}, {0, 0}};
+    uint32_t serial = 0;               // device-route calls so far: the call with serial n writes table n & 1
+    PinBuf dup;                        // set by the kernel when a window occurs in two paths of the set
+    bool taken = false;                // the current call takes the device route
+    bool check_dup = false;            // the last launch took it: the blocking call reads the duplicate flag
+    bool image_stale = false;          // the host images do not hold the current set
+    std::vector<std::vector<uint64_t>> shared;  // memo combinations (id << 32 | serial per path) known to share windows
+    size_t shared_next = 0;
+    std::vector<uint64_t> key;         // this call's combination
+    int64_t dev_calls = 0, host_calls = 0, fallbacks = 0, compactions = 0;
+    void release() {
+      for (int mt = 0; mt < 2; mt++) {
+        pool[mt].release(); stamp[mt].release();
+        for (int k = 0; k < 2; k++) { tab[mt][k].release(); list[mt][k].release(); }
+      }
+      stage.release(); dup.release();
+    }
+  } occdev;
   int64_t batches_patched = 0, batches_full = 0;  // gaml_hip_calc_prob_batch chunks whose per-set tables were built on the device from patches / written whole
   size_t batch_slack = 0;             // extra bytes per path set region of a batch (grows when a set's tables did not fit)
   hipEvent_t ev_tables = nullptr, ev_ovf = nullptr;
@@ -456,6 +486,7 @@ struct gaml_hip_ctx {
   // dispatch of its own for them (multi.hip: ctx_set_status / ctx_status_done)
   double* status_dst = nullptr; double status_a = 0, status_b = 0; bool status_done = false;
   bool host_results = false;  // blocking call: kernels write their results into pinned host memory, no D2H copy
+  bool occ_route = false;     // gaml_hip_calc_partials: whole-set calls may build their occurrence tables on the device (occ_device.hip.h)
   // sharded evaluation with a coverage penalty: sweeps wait for the other ranks' coverage maps
   bool defer_cov = false;
   struct PendingCov { int paired_idx; CovArgs args; double* out4; };

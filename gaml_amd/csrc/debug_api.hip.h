@@ -18,7 +18,7 @@ int gaml_hip_debug_prepare(gaml_hip_ctx* c, const int32_t* flat, const int64_t* 
       PairedSet& ps = *c->paireds[h.idx];
       if (int e = prepare_paired_structure(c, ps, flat, offs, n_paths)) return e;
       if (int e = align_pending_pair(c, ps)) return e;
-      prepare_paired_tables_host(c, ps, p);
+      if (int e = prepare_paired_tables_host(c, ps, p)) return e;
     }
   }
   if (c->peers == 1) {
@@ -48,6 +48,7 @@ int64_t gaml_hip_debug_table_occurrences(gaml_hip_ctx* c, int rs, int mate, int3
   PairedSet& ps = *c->paireds[c->handles[rs].idx];
   if (info3) { info3[0] = ps.planner.last_was_incremental(); info3[1] = (int64_t)ps.planner.incremental_calls; info3[2] = (int64_t)ps.planner.full_calls; }
   std::vector<Occ> v;
+  paired_images_refresh(ps);
   ps.image[mate].dump(v);
   const std::vector<int32_t>& slots = ps.planner.slots();
   std::unordered_map<int32_t, int32_t> pos;
@@ -327,4 +328,43 @@ int gaml_hip_debug_tables_check(gaml_hip_ctx* c, int rs, int64_t* out8) {
   out8[6] = compared; out8[7] = bad;
   T.release();
   return bad ? fail(c, GAML_HIP_ESTATE, "record tables: the device build differs from the host restatement") : GAML_HIP_OK;
+}
+
+int gaml_hip_debug_occ_route(gaml_hip_ctx* c, int rs, int64_t* out6) {
+  MULTI_SHARD0(c);
+  if (!c || !out6 || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const PairedSet::OccDev& D = c->paireds[c->handles[rs].idx]->occdev;
+  out6[0] = D.dev_calls; out6[1] = D.host_calls; out6[2] = D.fallbacks; out6[3] = D.compactions;
+  out6[4] = (int64_t)(D.pool_used[0] + D.pool_used[1]); out6[5] = (int64_t)D.shared.size();
+  return GAML_HIP_OK;
+}
+
+int gaml_hip_debug_occ_check(gaml_hip_ctx* c, int rs, int64_t* out4) {
+  MULTI_SHARD0(c);
+  if (!c || !out4 || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  PairedSet& ps = *c->paireds[c->handles[rs].idx];
+  const PairedSet::OccDev& D = ps.occdev;
+  out4[0] = out4[1] = out4[2] = out4[3] = 0;
+  if (!D.image_stale) return GAML_HIP_OK;  // the last call did not take the device route (or the images were rebuilt since)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const PlanView& v = ps.planner.view();
+  for (int mt = 0; mt < 2; mt++) {
+    OccImage im;  // what the host route would have written for this set
+    im.build(ps.mate[mt].wins.size(), v, mt);
+    const size_t n = im.occ12.size();
+    std::vector<Occ12> dev(n);
+    if (n) HIP_TRY(c, hipMemcpy(dev.data(), occdev_table(ps, mt), n * sizeof(Occ12), hipMemcpyDeviceToHost));
+    for (size_t w = 0; w < n; w++) {
+      const Occ12& h = im.occ12[w];
+      const Occ12& d = dev[w];
+      const bool absent = h.lo == ~0u && h.hi == ~0u;
+      out4[0]++;
+      if (!absent) out4[1]++;
+      if (absent ? (d.lo != ~0u || d.hi != ~0u) : (d.lo != h.lo || d.hi != h.hi || d.rank != h.rank)) out4[2]++;
+    }
+    if (!im.general_wids.empty()) out4[3]++;
+  }
+  if (out4[2] || out4[3]) return fail(c, GAML_HIP_ESTATE, "device occurrence tables differ from the host image");
+  return GAML_HIP_OK;
 }

@@ -226,6 +226,7 @@ std::vector<Walk> unflatten(const int32_t* flat, const int64_t* offs, int32_t n)
 
 }  // namespace
 
+#include "occ_device.hip.h"
 #include "paired_launch.hip.h"
 
 namespace {
@@ -514,7 +515,7 @@ void gaml_hip_destroy(gaml_hip_ctx* c) {
                                     s->dl_rec[m].release(); s->sp_rng[m].release(); s->sp_rec[m].release(); }
       s->dl_slot.release(); s->dl_spill.release(); s->sp_slot.release(); s->dstate.release(); s->dl_bins.release(); s->dl_bin_count.release(); s->dl_blk_tot.release(); s->dl_wlist.release(); s->h_dstate.release(); s->lcode.release(); s->len_combo_dev.release(); s->combo_tabs.release(); s->memo.release();
       drop_stage(s->stage_pool); s->h_part_sum.release(); s->h_part_zero.release(); s->h_timeline.release();
-      s->probs.release(); s->tabs.release(); s->arena.release(); s->persist.release(); s->cov_bits.release(); s->bad.release(); if (s->ev_tables) (void)hipEventDestroy(s->ev_tables); if (s->ev_ovf) (void)hipEventDestroy(s->ev_ovf);
+      s->probs.release(); s->tabs.release(); s->arena.release(); s->persist.release(); s->occdev.release(); s->cov_bits.release(); s->bad.release(); if (s->ev_tables) (void)hipEventDestroy(s->ev_tables); if (s->ev_ovf) (void)hipEventDestroy(s->ev_ovf);
       s->red.release();
     }
     for (auto& s : c->pacbios) { s->d_lens.release(); s->rec_off.release(); s->rec_walk.release(); s->rec_logp.release(); s->walk_count.release(); s->logprobs.release(); s->red.release(); drop_stage(s->stage);
@@ -1080,7 +1081,28 @@ int gaml_hip_calc_partials(gaml_hip_ctx* c, const int32_t* paths, const int64_t*
   void* dres = nullptr;
   HIP_TRY(c, hipHostGetDevicePointer(&dres, c->packed_host.p, 0));
   c->host_results = true;
+  c->occ_route = true;
   int e = evaluate(c, paths, offs, n_paths, dres, c->stream, total_len_out);
+  c->occ_route = false;
+  c->host_results = false;
+  if (e) return e;
+  if (int e2 = fetch_partials(c, partials_out)) return e2;
+  // a set whose tables the device built and found a window in two of its paths: those need the lists only the host
+  // route builds. Its partials are discarded and the evaluation's pass 2 and launches run again on the host route.
+  bool redo = false;
+  for (auto& ps : c->paireds) {
+    PairedSet::OccDev& D = ps->occdev;
+    if (!D.check_dup) continue;
+    D.check_dup = false;
+    if (*(volatile int*)D.dup.p == 0) continue;
+    occdev_note_shared(D);
+    D.fallbacks++;
+    redo = true;
+  }
+  if (!redo) return GAML_HIP_OK;
+  c->host_results = true;
+  c->pending_open = true;
+  e = eval_finish(c, dres, c->stream);
   c->host_results = false;
   if (e) return e;
   return fetch_partials(c, partials_out);
@@ -1115,14 +1137,18 @@ static int wait_host_partials(gaml_hip_ctx* c, bool* spun) {
   if (spin) {
     const double deadline = t0 + 2e6;
     for (auto& ps : c->paireds) {
+      // a set whose occurrence tables the device built with a window in two paths: its partials are discarded (and may
+      // not even pass the sentinel test) -- the scatter kernel raised the flag before the scoring launch began
+      const volatile int* dup = ps->occdev.check_dup ? (const volatile int*)ps->occdev.dup.p : nullptr;
       for (int k = 0; k < ps->last_sets && spin; k++) {
         const volatile double* hs = (const volatile double*)ps->h_part_sum.p + (size_t)k * ps->host_part_stride;
         const volatile int* hz = (const volatile int*)ps->h_part_zero.p + (size_t)k * ps->host_part_stride;
         int done = 0;
+        unsigned polls = 0;
         while (done < ps->last_blocks[k]) {
           if (hs[done] == hs[done] && hz[done] != INT_MIN) { done++; continue; }  // NaN != NaN
           __builtin_ia32_pause();
-          if ((done & 63) == 0 && now_us() > deadline) { spin = false; break; }
+          if ((++polls & 63) == 0 && ((dup && *dup) || now_us() > deadline)) { spin = false; break; }
         }
       }
       if (!spin) break;
@@ -1221,6 +1247,7 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* c, int32_t n_sets, const int32_t* pat
   if (c->device < 0) return fail(c, GAML_HIP_ENODEVICE, "scoring needs a HIP device: this context is host-only");
   if (n_sets == 0) return GAML_HIP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
+  for (auto& ps : c->paireds) paired_images_refresh(*ps);  // the batch routes patch the images from the current set's
   const size_t ns = std::max<size_t>(1, c->handles.size());
   for (int32_t i = 0; i < n_sets; i++) if (set_offs[i + 1] < set_offs[i]) return fail(c, GAML_HIP_EINVAL, "set offsets must not decrease");
   int32_t done_sets = 0;

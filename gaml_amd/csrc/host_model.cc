@@ -970,6 +970,14 @@ static void occ_prepack(const std::vector<Occ>& occ, std::vector<OccPre>& pre) {
   }
 }
 
+// what the device route asks of a memo: every entry direct, no window twice within the path
+static bool occ_pre_plain(const std::vector<OccPre>& pre) {
+  std::vector<int32_t> w(pre.size());
+  for (size_t k = 0; k < pre.size(); k++) { if (pre[k].wid < 0) return false; w[k] = pre[k].wid; }
+  std::sort(w.begin(), w.end());
+  return std::adjacent_find(w.begin(), w.end()) == w.end();
+}
+
 void PairedPlanner::invalidate_thresholds() {
   for (auto& pm : memos_) pm->occ_valid[0] = pm->occ_valid[1] = false;
   have_prev_ = false;  // every occurrence list changes: the next call rebuilds the tables from scratch
@@ -984,6 +992,8 @@ void PairedPlanner::finish(ShortMate mate[2]) {
       pm.assembled[mt] = 0;
       for (const Occ& o : pm.occ[mt]) pm.assembled[mt] += mate[mt].wins[o.wid].count;
       occ_prepack(pm.occ[mt], pm.pre[mt]);
+      pm.pre_plain[mt] = occ_pre_plain(pm.pre[mt]);
+      pm.dev_off[mt] = -1;  // the device copy of pre[] is out of date
       pm.occ_valid[mt] = true;
     }
   };
@@ -1005,7 +1015,7 @@ const PlanView& PairedPlanner::view() {
   return view_;
 }
 
-void PairedPlanner::apply(ShortMate mate[2], OccImage image[2]) {
+void PairedPlanner::apply(ShortMate mate[2], OccImage image[2], bool build_image, bool image_stale) {
   if (!incremental_) {
     const PlanView& v = view();
     for (int32_t id : cur_ids_) {
@@ -1014,7 +1024,22 @@ void PairedPlanner::apply(ShortMate mate[2], OccImage image[2]) {
       for (int mt = 0; mt < 2; mt++) for (const Occ& o : pm.occ[mt]) mate[mt].touch(o.wid);  // a memoised list may name windows a rebuild retired
       pm.touched_serial = retire_serial_;
     }
-    for (int mt = 0; mt < 2; mt++) image[mt].build(mate[mt].wins.size(), v, mt);
+    if (build_image) for (int mt = 0; mt < 2; mt++) image[mt].build(mate[mt].wins.size(), v, mt);
+    return;
+  }
+  if (image_stale) {
+    // the images hold some earlier set, not the previous call's: this call's set whole (its slots as the diff assigned them)
+    for (int mt = 0; mt < 2; mt++) {
+      for (const Removed& r : removed_) assembled_[mt] -= r.assembled[mt];
+      for (int32_t k : work_) assembled_[mt] += memos_[cur_ids_[k]]->assembled[mt];
+    }
+    for (int32_t id : cur_ids_) {
+      PathMemo& pm = *memos_[id];
+      if (pm.touched_serial == retire_serial_) continue;
+      for (int mt = 0; mt < 2; mt++) for (const Occ& o : pm.occ[mt]) mate[mt].touch(o.wid);
+      pm.touched_serial = retire_serial_;
+    }
+    rebuild_images(mate, image);
     return;
   }
   for (int32_t k : work_) {
@@ -1035,6 +1060,13 @@ void PairedPlanner::apply(ShortMate mate[2], OccImage image[2]) {
     }
     im.finalize(pos_of_slot_);
   }
+}
+
+void PairedPlanner::rebuild_images(ShortMate mate[2], OccImage image[2]) {
+  if ((int32_t)pos_of_slot_.size() < next_slot_) pos_of_slot_.resize((size_t)next_slot_ + 64, 0);
+  for (int32_t k = 0; k < (int32_t)cur_slots_.size(); k++) pos_of_slot_[cur_slots_[k]] = k;
+  const PlanView& v = view();
+  for (int mt = 0; mt < 2; mt++) image[mt].build(mate[mt].wins.size(), v, mt, &cur_slots_, &pos_of_slot_);
 }
 
 void PairedPlanner::mark_used(ShortMate mate[2], const OccImage image[2]) {
@@ -1470,7 +1502,8 @@ void OccImage::dump(std::vector<Occ>& out) const {
   }
 }
 
-void OccImage::build(size_t n_windows, const PlanView& view, int mate) {
+void OccImage::build(size_t n_windows, const PlanView& view, int mate, const std::vector<int32_t>* slots,
+                     const std::vector<int32_t>* pos_of_slot) {
   grow(n_windows);
   // The previous set's entries are cleared AFTER the new ones are written, and only where the new set has none: path
   // sets of one assembly mostly name the same windows, whose entries would otherwise be written twice.
@@ -1482,8 +1515,9 @@ void OccImage::build(size_t n_windows, const PlanView& view, int mate) {
   // with the path's occurrence list: only the path slot is added here); a second occurrence moves the first one to
   // the window's list (the entry holds everything a list entry needs: a filter threshold clamped at -32768 filters like
   // the exact one, positions are >= 0).
-  for (size_t slot = 0; slot < view.paths.size(); slot++) {
-    const PathMemo& pm = *view.paths[slot];
+  for (size_t pos = 0; pos < view.paths.size(); pos++) {
+    const PathMemo& pm = *view.paths[pos];
+    const size_t slot = slots ? (size_t)(*slots)[pos] : pos;
     const std::vector<OccPre>& pre = pm.pre[mate];
     const bool slot_fits = slot < 32767;
     const uint32_t slot_bits = (uint32_t)(slot & 0x7fff) << 16;
@@ -1507,6 +1541,7 @@ void OccImage::build(size_t n_windows, const PlanView& view, int mate) {
   for (int32_t w : stale_) if (stamp_[w] != serial_ && cnt_[w]) { occ12[w] = Occ12{~0u, ~0u, 0}; cnt_[w] = 0; }
   changed_all = true;
   lists_dirty_ = true;
+  if (pos_of_slot) { finalize(*pos_of_slot); return; }
   std::vector<int32_t> ident(view.paths.size());
   for (size_t k = 0; k < ident.size(); k++) ident[k] = (int32_t)k;  // slots are positions here
   finalize(ident);

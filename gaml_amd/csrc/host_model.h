@@ -267,7 +267,9 @@ struct OccImage {
   std::vector<OccQuad> multi;
   std::vector<int32_t> general_wids;  // windows whose entry sends their reads to the general path
   // whole path set at once (every path changed, first call, coverage penalty): O(occurrences)
-  void build(size_t n_windows, const PlanView& view, int mate);
+  // slots: the path slot of every path of the set (null: slots are positions), pos_of_slot its inverse
+  void build(size_t n_windows, const PlanView& view, int mate, const std::vector<int32_t>* slots = nullptr,
+             const std::vector<int32_t>* pos_of_slot = nullptr);
   // one path's occurrences in or out (a call that shares most paths with the previous one): O(its occurrences).
   // `slot` is what the entries carry as their path (stable while the path stays in the set; only equality of the
   // two mates' paths matters to the scorers), the rank is path-local (it only ever orders occurrences of one path).
@@ -320,6 +322,9 @@ struct PathMemo {
   std::vector<Placement> pl[2];          // shifts relative to the path start, path = 0
   std::vector<Occ> occ[2];               // rank path-local, path = 0
   std::vector<OccPre> pre[2];            // the same occurrences as table entries minus the path slot (OccImage::build)
+  bool pre_plain[2] = {false, false};    // every entry of pre[] is direct (wid >= 0) and names a window once within the path
+  int64_t dev_off[2] = {-1, -1};         // where pre[] sits in the device pool of its set (-1: not there; set by the launcher)
+  uint32_t dev_gen[2] = {0, 0};          // ... valid while the pool's generation is this (a compaction moves everything)
   int64_t assembled[2] = {0, 0};         // records of the occurring windows
   std::vector<int32_t> starts;           // contig start coordinates (events of type 1, graph.cc:1826,1835)
   int32_t length = 0;                    // incl. gaps
@@ -346,7 +351,13 @@ class PairedPlanner {
              bool allow_incremental, std::string* err);
   void finish(ShortMate mate[2]);          // pass 2 (needs the windows' records / global maxima): occurrence lists
   // the occurrence tables of this call: whole-set rebuild or per-path adds / removes (what begin() decided)
-  void apply(ShortMate mate[2], OccImage image[2]);
+  // build_image = false: the device builds this call's tables (whole-set calls only; the images go stale).
+  // image_stale: the images do not hold the previous call's set -- an incremental call rebuilds them whole.
+  void apply(ShortMate mate[2], OccImage image[2], bool build_image = true, bool image_stale = false);
+  // the images for the current set, whole (a consumer of the images after calls whose tables the device built)
+  void rebuild_images(ShortMate mate[2], OccImage image[2]);
+  const std::vector<int32_t>& ids() const { return cur_ids_; }     // memo of every path of the current set
+  PathMemo& memo(int32_t id) { return *memos_[id]; }
   // table rebuilds retire windows no path set has used since the previous rebuild: mark_used() marks the windows of
   // the current set and of every path that entered a set since the last call of note_rebuild()
   void mark_used(ShortMate mate[2], const OccImage image[2]);

@@ -83,11 +83,17 @@ int prepare_paired_structure(gaml_hip_ctx* c, PairedSet& s, const int32_t* flat,
 }
 
 // pass 2: position-filter thresholds (need the windows' global largest positions) + occurrence images
-void prepare_paired_tables_host(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p) {
-  (void)c;
+// A whole-set call that qualifies (occdev_route_ok) sends its descriptors right here: the scatter kernel runs while the
+// host finishes pass 2 and prepares the scoring launch. (`st`: the stream of the scoring launch; null: no device route.)
+int prepare_paired_tables_host(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, hipStream_t st = nullptr, bool device_route = false) {
   static const bool trace = getenv("GAML_HIP_TRACE_HOST") != nullptr;
   const double q0 = now_us();
   s.planner.finish(s.mate);
+  PairedSet::OccDev& D = s.occdev;
+  D.taken = device_route && occdev_route_ok(c, s);
+  size_t up_bytes = 0;
+  if (D.taken) { if (int e = occdev_launch(c, s, st, &up_bytes)) return e; }
+  c->prof[6] = (double)up_bytes;
   const double q1 = now_us();
   const bool cov = s.cfg.penalty_constant > 0;
   // coverage bitmap layout + contig starts (events of type 1, graph.cc:1826,1833-1835)
@@ -108,10 +114,14 @@ void prepare_paired_tables_host(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p) {
   p.total_bits = p.path_base.back();
   p.n_paths = s.planner.n_paths();
   const double q2 = now_us();
-  s.planner.apply(s.mate, s.image);  // the occurrence tables: whole-set rebuild, or the changed paths' entries in / out
+  // the occurrence tables: whole-set rebuild, or the changed paths' entries in / out (or, on the device route, neither)
+  s.planner.apply(s.mate, s.image, !D.taken, D.image_stale);
+  D.image_stale = D.taken;
+  if (D.taken) D.dev_calls++; else D.host_calls++;
   p.assembled_records = s.planner.assembled(0) + s.planner.assembled(1);
-  p.general = !s.image[0].general_wids.empty() || !s.image[1].general_wids.empty();
+  p.general = !D.taken && (!s.image[0].general_wids.empty() || !s.image[1].general_wids.empty());
   if (trace) fprintf(stderr, "pass2: finish %.1f us, starts %.1f us, images %.1f us\n", q1 - q0, q2 - q1, now_us() - q2);
+  return 0;
 }
 
 }  // namespace
@@ -448,7 +458,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   const double tpp = now_us();
   if (int e = prepare_paired_tables(c, s)) return e;
   const double tp0 = now_us();
-  prepare_paired_tables_host(c, s, p);  // pass 2 (pass 1 ran in eval_begin)
+  if (int e = prepare_paired_tables_host(c, s, p, st, true)) return e;  // pass 2 (pass 1 ran in eval_begin)
   const double t_after_host = now_us();
   c->prof[1] = t_after_host - tp0;  // thresholds + occurrence tables
   gpu_probe(st, c->warm_buf.p, "before table sync");
@@ -461,13 +471,23 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   const int tl = total_len == 0 ? 1 : total_len;
   // blocking call on a large-BAR device: the resident copy of the tables is patched in place (a few entries when the
   // path set shares most paths with the previous call's); otherwise a ring slot receives the whole tables
-  const bool resident = c->host_results && c->direct_write && KNOB(c, 8) == 0 && KNOB(c, 13) == 0 && !cov;
+  const bool resident = paired_resident_route(c, s);
   PairedLayout L;
   memset(&L, 0, sizeof(L));
   int slot = -1;
   const char* arena = nullptr;
   SetDev sd;
-  if (resident) {
+  s.occdev.check_dup = s.occdev.taken;
+  if (s.occdev.taken) {
+    // device route: occ_scatter_kernel (queued in pass 2) builds this call's tables; only the thresholds go through the BAR
+    PairedLayout Lt;
+    Lt.tfloor_off = s.persist.off_tfloor;
+    paired_pack_thresholds(s, Lt, (double)(2 * tl), (char*)s.persist.dev);
+    _mm_sfence();
+    paired_persist_view(s, total_len, sd);
+    for (int mt = 0; mt < 2; mt++) sd.occ12[mt] = occdev_table(s, mt);
+    c->prof[6] += 256.0 * sizeof(double);
+  } else if (resident) {
     c->prof[6] = (double)((s.image[0].changed_all || s.image[1].changed_all || !s.persist.valid) ? (s.image[0].occ12.size() + s.image[1].occ12.size()) * sizeof(Occ12)
                                                                                             : (s.image[0].changed.size() + s.image[1].changed.size()) * sizeof(Occ12));
     if (int e = paired_persist_update(c, s, (double)(2 * tl), st)) return e;

@@ -61,6 +61,7 @@ int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int
  * blocks left out (TIMING ONLY, results wrong), 12 = 1: every path set planned from scratch, 13 = 1: whole per-call tables
  * through the ring (no resident copy), 14 = 1: every table build on the calling stream, k > 1: a build beside the
  * evaluations takes over k evaluations after its start (default 96), 15 = 1: rebuilds never retire unused windows,
+ * 17 = 1: whole-set calls build their occurrence tables on the host (no device route, occ_device.hip.h),
  * 16 = 1: record tables keep the records that can never survive the overwrite rule (takes effect at the next table build;
  * same values either way), 18 = d: tables are rebuilt when the delta lists pass pairs / d (default 8), 19 = 1: no static
  * memo indices (takes effect at the next table build; same values either way), 20 = blocks of the compact class's second
@@ -101,6 +102,16 @@ int gaml_hip_debug_tables_check(gaml_hip_ctx* ctx, int readset, int64_t* out8);
  * compact class, up to the <= 2-record class, up to the <= 4-record class, lane-per-pair blocks, all scoring blocks,
  * 0, partials}. Returns the number of partials. For bit-equality hunts between routes. */
 int32_t gaml_hip_debug_block_partials(gaml_hip_ctx* ctx, int readset, int32_t set, double* sums, int32_t* zeros, int32_t cap, int32_t* layout8);
+
+/* Occurrence tables of whole-set calls built on the device (gaml_amd/csrc/occ_device.hip.h), paired set `readset`:
+ * out6 = {calls whose tables the device built, calls whose tables the host built, device-route calls evaluated again on
+ * the host route because two paths share a window, pool compactions, pool entries in use (both mates), memo combinations
+ * known to share windows}. */
+int gaml_hip_debug_occ_route(gaml_hip_ctx* ctx, int readset, int64_t* out6);
+/* When the last call took the device route: its device tables copied back and compared entry by entry with the host image
+ * built for the same set. out4 = {entries compared, entries present, mismatches, mates whose host image needs lists};
+ * GAML_HIP_ESTATE when they differ. All zeros when the last call did not take the route. */
+int gaml_hip_debug_occ_check(gaml_hip_ctx* ctx, int readset, int64_t* out4);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 """Where one blocking CalcProb goes (cfg3 by default), per upload route (knob 8: 0 = host writes device memory through the
-BAR, 1 = staging + hipMemcpyAsync, 2 = staging + copy kernel): medians of gaml_hip_debug_profile over 400 steps.
+BAR, 1 = staging + hipMemcpyAsync, 2 = staging + copy kernel) and occurrence-table route (knob 17: 0 = whole-set calls
+build them on the device, 1 = on the host): medians of gaml_hip_debug_profile over 400 steps.
   python tools/phase_profile.py [cfg3|cfg2] [batch]"""
 import os, sys, time
 os.environ.setdefault("GAML_HIP_FLAVOUR", "dev")  # tools look inside the library: the development build
@@ -18,14 +19,17 @@ vp = bench.path_variants(synth.genome_walk(g))
 variants = [api.FlatPaths(v) for v in vp]
 [ctx.score(v) for v in variants]; ctx.compact_tables(); ctx.score(variants[0])
 names = ["pass1", "tables_host", "-", "pack/write", "table_sync", "launch", "bytes", "wait"]
-for knob in (0, 2, 1, 0):
-    ctx.debug_set_knob(8, knob)
+# knob 8: upload route; knob 17 = 1: whole-set calls build their occurrence tables on the host (no device route)
+for knob, value in ((8, 0), (8, 2), (8, 1), (8, 0), (17, 1), (17, 0), (17, 1), (17, 0)):
+    ctx.debug_set_knob(knob, value)
     for i in range(50): ctx.score(variants[i % 8])
     prof, ts = [], []
     for i in range(400):
         t = time.perf_counter(); ctx.score(variants[i % 8]); ts.append((time.perf_counter() - t) * 1e6); prof.append(ctx.debug_profile())
     med = np.median(np.array(prof), axis=0)
-    print(f"knob8={knob}: step median {np.median(ts):.1f} us p90 {np.percentile(ts, 90):.1f} | " + ", ".join(f"{n} {v:.1f}" for n, v in zip(names, med) if n != "-"))
+    print(f"knob{knob}={value}: step median {np.median(ts):.1f} us p90 {np.percentile(ts, 90):.1f} | " + ", ".join(f"{n} {v:.1f}" for n, v in zip(names, med) if n != "-"))
+    ctx.debug_set_knob(knob, 0)
+print("routes:", ctx.debug_occ_route(rs) if hasattr(ctx, "debug_occ_route") else "n/a")
 if len(sys.argv) > 2:
     bp = api.BatchPaths(vp)
     for knob11 in (0, 1, 0):
