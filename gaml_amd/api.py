@@ -223,6 +223,12 @@ def _load():
     if hasattr(L, "gaml_hip_fetch_async"):
         L.gaml_hip_fetch_async.argtypes = [vp, C.c_void_p, C.c_int32, C.c_void_p]
         L.gaml_hip_fetch_wait.argtypes = [vp, C.c_void_p, C.c_int32]
+    if hasattr(L, "gaml_hip_advice_build"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_advice_build.argtypes = [vp, C.c_int, C.c_int32]
+        L.gaml_hip_advice_index.argtypes = [vp, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+        L.gaml_hip_advice_index.restype = C.c_int64
+        L.gaml_hip_advice_candidates.argtypes = [vp, C.c_int, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+        L.gaml_hip_advice_candidates.restype = C.c_int64
     if hasattr(L, "gaml_hip_debug_timeline"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_debug_timeline.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64]
     L.gaml_hip_last_phases.argtypes = [vp, _f64p]
@@ -660,6 +666,40 @@ class Context:
     def align_window(self, rs, mate, walk) -> int:
         walk = np.ascontiguousarray(walk, np.int32)
         return _lib.gaml_hip_align_window(self._h, rs, mate, walk, len(walk))
+
+    # ---- the advice move of a paired set (ExtendPathsAdv moves.cc:933-998)
+    def advice_build(self, rs, threshold: int):
+        """BuildAdviceIndex on mate 2 (graph.cc:323-342); once per read set, the first threshold stays."""
+        self._check(_lib.gaml_hip_advice_build(self._h, rs, int(threshold)))
+
+    def advice_index(self, rs):
+        """(offs[n_pairs + 1], nodes, orient1): pair r's advice nodes are nodes[offs[r]:offs[r + 1]], ascending; orient1
+        marks the ones in GetAdviceIndex1 (the pair's first record in the node's window has orientation 1)."""
+        offs = np.zeros(self.readset_reads(rs) + 1, np.int64)
+        total = self._check(_lib.gaml_hip_advice_index(self._h, rs, offs.ctypes.data, None, 0))
+        ent = np.zeros(max(1, total), np.int32)
+        self._check(_lib.gaml_hip_advice_index(self._h, rs, offs.ctypes.data, ent.ctypes.data, total))
+        ent = ent[:total]
+        return offs, ent >> 1, (ent & 1).astype(bool)
+
+    def advice_candidates(self, rs, path, reach=(), only_out=True, allow_gaps=False, cap=None):
+        """`cands` of moves.cc:956-986 for `path` (already reversed by the caller if it wanted to); reach: the keys of
+        reach_limit_[path.back()]. Returns the list; with `cap`, (count, the first cap entries) of one call."""
+        path = np.ascontiguousarray(path, np.int32)
+        reach = np.ascontiguousarray(list(reach), np.int32)
+        flags = (1 if only_out else 0) | (2 if allow_gaps else 0)
+        if cap is not None:
+            out = np.zeros(max(1, cap), np.int32)
+            n = self._check(_lib.gaml_hip_advice_candidates(self._h, rs, path, len(path), reach, len(reach), flags, out.ctypes.data, cap))
+            return n, out[:min(n, cap)]
+        out = getattr(self, "_adv_buf", None)
+        if out is None:
+            out = self._adv_buf = np.zeros(1 << 14, np.int32)
+        n = self._check(_lib.gaml_hip_advice_candidates(self._h, rs, path, len(path), reach, len(reach), flags, out.ctypes.data, len(out)))
+        if n > len(out):  # a repeat of the call returns the same list
+            out = self._adv_buf = np.zeros(n, np.int32)
+            n = self._check(_lib.gaml_hip_advice_candidates(self._h, rs, path, len(path), reach, len(reach), flags, out.ctypes.data, len(out)))
+        return out[:n].copy()
 
     def debug_prepare(self, paths):
         flat, offs = _flat(paths)

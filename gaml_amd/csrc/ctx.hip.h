@@ -260,6 +260,27 @@ struct PairInfo {
   int64_t dropped_records[2] = {0, 0};
 };
 
+// the advice move of a paired set (advice.hip.h): the index over this shard's pairs and the buffers of a query
+struct AdviceDev {
+  bool built = false;
+  int32_t threshold = 0;
+  int64_t n_ent = 0, queries = 0;
+  std::vector<int64_t> h_offs;          // host-only contexts: the index on the host
+  std::vector<int32_t> h_ent;
+  DevBuf offs, ent;                     // the index, resident: CSR over the pairs, entries node << 1 | orient1
+  DevBuf scratch;                       // build: sort keys / payloads, flags, places, scan tiles
+  DevBuf first, last, cnt, at, tiles;   // query: per-pair keys (stamped with the call's serial), counts, places
+  DevBuf in, mask, out;                 // query: steps | path | reach, exclusion + reach bits, the list
+  PinBuf h_in, h_out;
+  uint32_t serial = 0;
+  std::vector<AdviceStep> steps;        // the last query's walk ...
+  std::vector<int32_t> list;            // ... and its candidates
+  void release() {
+    offs.release(); ent.release(); scratch.release(); first.release(); last.release(); cnt.release(); at.release(); tiles.release();
+    in.release(); mask.release(); out.release(); h_in.release(); h_out.release();
+  }
+};
+
 struct PairedSet {
   gaml_paired_cfg cfg;
   ShortMate mate[2];
@@ -349,6 +370,7 @@ struct PairedSet {
   bool floor_positive = true;  // every floor exp(c + k s) > 0 (else "probability 0 is floored" does not hold: no memo / shortcut paths)
   bool tabs_uploaded = false;
   int64_t last_bad_bases = 0;
+  AdviceDev adv;
 };
 
 struct SingleSet {
@@ -443,6 +465,7 @@ struct gaml_hip_ctx {
   std::vector<std::unique_ptr<PacbioSet>> pacbios;
   std::vector<SetRef> handles;  // creation order -> (kind, index)
   int32_t rank = 0, world = 1;
+  bool multi_shard = false;  // one of the shards of a multi-device context (gaml_hip_create_multi)
   AlignScratch aln_scratch;
   AlignSmall aln_small[2];
   int64_t aln_windows = 0, aln_candidates = 0;  // GPU aligner statistics

@@ -424,6 +424,7 @@ int ctx_fetch_wait_bounded(gaml_hip_ctx* c, double* out, int32_t n_doubles, doub
 void ctx_set_status(gaml_hip_ctx* c, double* dst, double a, double b) { c->status_dst = dst; c->status_a = a; c->status_b = b; c->status_done = false; }
 bool ctx_status_done(const gaml_hip_ctx* c) { return c->status_done; }
 void ctx_eval_abandon(gaml_hip_ctx* c) { if (c) { c->pending_open = false; c->pending_cov.clear(); c->pending_pb.clear(); } }
+void ctx_set_multi_shard(gaml_hip_ctx* c) { c->multi_shard = true; }
 bool ctx_has_penalty(const gaml_hip_ctx* c) {
   for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0) return true;
   for (auto& ps : c->pacbios) if (ps->cfg.penalty_constant > 0) return true;
@@ -516,7 +517,7 @@ void gaml_hip_destroy(gaml_hip_ctx* c) {
       s->dl_slot.release(); s->dl_spill.release(); s->sp_slot.release(); s->dstate.release(); s->dl_bins.release(); s->dl_bin_count.release(); s->dl_blk_tot.release(); s->dl_wlist.release(); s->h_dstate.release(); s->lcode.release(); s->len_combo_dev.release(); s->combo_tabs.release(); s->memo.release();
       drop_stage(s->stage_pool); s->h_part_sum.release(); s->h_part_zero.release(); s->h_timeline.release();
       s->probs.release(); s->tabs.release(); s->arena.release(); s->persist.release(); s->occdev.release(); s->cov_bits.release(); s->bad.release(); if (s->ev_tables) (void)hipEventDestroy(s->ev_tables); if (s->ev_ovf) (void)hipEventDestroy(s->ev_ovf);
-      s->red.release();
+      s->red.release(); s->adv.release();
     }
     for (auto& s : c->pacbios) { s->d_lens.release(); s->rec_off.release(); s->rec_walk.release(); s->rec_logp.release(); s->walk_count.release(); s->logprobs.release(); s->red.release(); drop_stage(s->stage);
       s->d_bases.release(); s->dp.release(); s->sweep.release(); }
@@ -1494,3 +1495,5 @@ int gaml_hip_kernel_stats(gaml_hip_ctx* c, int reset, int64_t* launches, double*
 }
 
 }  // extern "C"
+
+#include "advice.hip.h"

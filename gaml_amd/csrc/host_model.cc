@@ -580,6 +580,103 @@ void register_for_contig(const GraphStore& g, ShortMate& m, const int32_t* ctg, 
 }
 
 // ---------------------------------------------------------------------------------------
+// advice move (ExtendPathsAdv moves.cc:933-998)
+// ---------------------------------------------------------------------------------------
+void advice_register_index(const GraphStore& g, ShortMate& m, int32_t threshold, std::vector<int32_t>& wids) {
+  // GetPositionsOnlyPath({i}, 0) per long node: GetSubpathsFromPath registers [i] when it is absent (graph.cc:327-332)
+  wids.clear();
+  for (int32_t i = 0; i < g.n(); i++) {
+    if (g.len(i) <= threshold) continue;
+    const Walk w(1, i);
+    const int32_t id = m.find(w);
+    wids.push_back(id >= 0 ? id : m.align(g, w));
+  }
+}
+
+void advice_walk(const GraphStore& g, const ShortMate& m, const int32_t* path, int32_t n, std::vector<AdviceStep>& out) {
+  out.clear();
+  int32_t cur_pos = 0;
+  Walk w;
+  for (int32_t i = 0; i < n; i++) {
+    if (path[i] < 0) { cur_pos += -path[i]; continue; }
+    junction(g, path, n, i, true, w);
+    int32_t ids[2] = {m.find(w), -1};
+    if (g.len(path[i]) > kTail && w.size() > 1) ids[1] = m.find(Walk(1, path[i]));
+    for (int32_t id : ids)
+      if (id >= 0 && m.wins[id].count > 0) out.push_back(AdviceStep{id, cur_pos});
+    cur_pos += g.len(path[i]);
+  }
+}
+
+void advice_host_spans(const ShortMate& m, const std::vector<int32_t>& wids, const std::vector<int32_t>& at, std::vector<AdviceSpan>& out) {
+  out.clear();
+  for (size_t k = 0; k < wids.size(); k++) {
+    const Window& w = m.wins[wids[k]];
+    out.push_back(AdviceSpan{w.count ? m.pool.data() + w.first : nullptr, w.count, at[k]});
+  }
+}
+
+void advice_index_host(int64_t n_pairs, const std::vector<AdviceSpan>& wins, std::vector<int64_t>& offs, std::vector<int32_t>& ent) {
+  // per pair and window the first record that passes the position filter (advice_index_ / advice_index1_, graph.cc:333-337);
+  // windows in node order, so a pair's entries come out ascending. Pass 0 counts, pass 1 writes.
+  const int64_t N = n_pairs;
+  std::vector<int32_t> seen;
+  std::vector<int64_t> at;
+  offs.assign((size_t)N + 1, 0);
+  for (int pass = 0; pass < 2; pass++) {
+    seen.assign((size_t)N, -1);
+    if (pass == 1) {
+      for (int64_t r = 0; r < N; r++) offs[r + 1] += offs[r];
+      ent.assign((size_t)offs[N], 0);
+      at.assign(offs.begin(), offs.end() - 1);
+    }
+    for (int32_t k = 0; k < (int32_t)wins.size(); k++) {
+      const AdviceSpan& w = wins[k];
+      for (int32_t q = 0; q < w.count; q++) {
+        const gaml_aligment& a = w.recs[q];
+        if (a.position < kAdviceMinPos || seen[a.read_id] == k) continue;
+        seen[a.read_id] = k;
+        if (pass == 0) offs[(size_t)a.read_id + 1]++;
+        else ent[(size_t)at[a.read_id]++] = w.at << 1 | (a.orientation & 1);
+      }
+    }
+  }
+}
+
+void advice_candidates_host(int64_t n_pairs, const std::vector<AdviceSpan>& steps, const std::vector<int64_t>& offs,
+                            const std::vector<int32_t>& ent, const int32_t* path, int32_t n, const int32_t* reach, int32_t n_reach,
+                            int32_t flags, int32_t n_nodes, std::vector<int32_t>& out) {
+  out.clear();
+  const int64_t N = n_pairs;
+  // positions_ (graph.cc:662-723): per pair its slots {absolute position, orientation} in order of appearance; a record at a
+  // position the pair already has rewrites that slot
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> slots((size_t)N);
+  for (const AdviceSpan& s : steps) {
+    for (int32_t q = 0; q < s.count; q++) {
+      const gaml_aligment& a = s.recs[q];
+      auto& v = slots[(size_t)a.read_id];
+      const int32_t abs_pos = a.position + s.at;
+      bool found = false;
+      for (auto& e : v)
+        if (e.first == abs_pos) { e.second = a.orientation; found = true; break; }
+      if (!found) v.emplace_back(abs_pos, a.orientation);
+    }
+  }
+  std::vector<char> excl((size_t)n_nodes, 0), in_reach((size_t)n_nodes, 0);
+  for (int32_t i = 0; i < n; i++) if (path[i] >= 0) { excl[(size_t)path[i]] = 1; excl[(size_t)(path[i] ^ 1)] = 1; }  // path_v (moves.cc:953-955)
+  for (int32_t i = 0; i < n_reach; i++) in_reach[(size_t)reach[i]] = 1;
+  for (int64_t r = 0; r < N; r++) {  // moves.cc:964-973
+    if (slots[(size_t)r].empty() || slots[(size_t)r][0].second != 0) continue;
+    for (int64_t q = offs[(size_t)r]; q < offs[(size_t)r + 1]; q++) {
+      const int32_t e = ent[(size_t)q], v = e >> 1;
+      if (!(e & 1)) continue;
+      if ((flags & GAML_HIP_ADVICE_ONLY_OUT) && excl[(size_t)v]) continue;
+      if ((flags & GAML_HIP_ADVICE_ALLOW_GAPS) || in_reach[(size_t)v]) out.push_back(v);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // occurrences
 // ---------------------------------------------------------------------------------------
 void placements_paired_contig(const GraphStore& g, const ShortMate& m, const int32_t* ctg, int32_t n, int32_t st,

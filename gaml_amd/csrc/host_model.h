@@ -153,6 +153,27 @@ uint64_t read_max_hash(const char* s, int32_t n);  // graph.cc:1254-1269
 void register_for_paths(const GraphStore& g, ShortMate& m, const std::vector<Walk>& paths);  // graph.cc:447-493
 void register_for_contig(const GraphStore& g, ShortMate& m, const int32_t* ctg, int32_t n);  // graph.cc:495-533, 538-542
 
+// advice move of a paired set (ExtendPathsAdv moves.cc:933-998; the device form is advice.hip.h)
+constexpr int32_t kAdviceMinPos = -5;  // BuildAdviceIndex reads one-node walks at st = 0: graph.cc:577 drops positions < max_pos - 5 = -5
+// BuildAdviceIndex (graph.cc:323-342): registers the one-node window of every node longer than `threshold`; their ids, node order
+void advice_register_index(const GraphStore& g, ShortMate& m, int32_t threshold, std::vector<int32_t>& wids);
+// rs.GetPositions (graph.cc:651-712) as the window lookups of its walk, in order: the window and its offset on the path.
+// Windows that are not cached or hold no record of this shard are left out, and so is the second look at a junction window
+// that is the node's own (it rewrites what the first look wrote).
+struct AdviceStep { int32_t wid, cur_pos; };
+void advice_walk(const GraphStore& g, const ShortMate& m, const int32_t* path, int32_t n, std::vector<AdviceStep>& out);
+// Host restatement (host-only contexts; the development build checks the device against it). It reads a window's
+// records as a span -- the host pool, or a device window copied back; local read ids -- tagged with the node (index)
+// or the offset on the path (walk step).
+struct AdviceSpan { const gaml_aligment* recs; int32_t count; int32_t at; };
+void advice_host_spans(const ShortMate& m, const std::vector<int32_t>& wids, const std::vector<int32_t>& at, std::vector<AdviceSpan>& out);
+// the index as CSR over the shard's pairs, entries node << 1 | orient1 (spans in node order, at = node) ...
+void advice_index_host(int64_t n_pairs, const std::vector<AdviceSpan>& wins, std::vector<int64_t>& offs, std::vector<int32_t>& ent);
+// ... and the candidate list of moves.cc:964-973 for a walk (spans in walk order, at = cur_pos)
+void advice_candidates_host(int64_t n_pairs, const std::vector<AdviceSpan>& steps, const std::vector<int64_t>& offs,
+                            const std::vector<int32_t>& ent, const int32_t* path, int32_t n, const int32_t* reach, int32_t n_reach,
+                            int32_t flags, int32_t n_nodes, std::vector<int32_t>& out);
+
 // occurrence lists
 // paired, pass 1 (structure): which cached windows sit where on a contig placed at path coordinate
 // `st` (GetPositionsOnlyPath graph.cc:544-573). Every cached window is listed, also one without

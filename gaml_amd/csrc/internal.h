@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/gaml_hip.h"
 #include "../../include/gaml_hip_debug.h"
@@ -40,6 +41,14 @@ void ctx_set_status(gaml_hip_ctx* c, double* dst, double a, double b);
 bool ctx_status_done(const gaml_hip_ctx* c);
 // close an evaluation that gaml_hip_eval_begin opened and that will not be finished (another shard failed)
 void ctx_eval_abandon(gaml_hip_ctx* c);
+// mark a context as one shard of a multi-device context
+void ctx_set_multi_shard(gaml_hip_ctx* c);
+// the advice move on this context's pairs (advice.hip.h): build; the index as CSR over its pairs; the candidate list
+// (*list: owned by the context, valid until its next call)
+int ctx_advice_build(gaml_hip_ctx* c, int rs, int32_t threshold);
+int ctx_advice_index(gaml_hip_ctx* c, int rs, std::vector<int64_t>& offs, std::vector<int32_t>& ent);
+int ctx_advice_candidates(gaml_hip_ctx* c, int rs, const int32_t* path, int32_t n, const int32_t* reach, int32_t n_reach, int32_t flags,
+                          const std::vector<int32_t>** list);
 
 
 // ---- implemented in multi.hip ------------------------------------------------------------------------------
@@ -81,6 +90,10 @@ int multi_bad_bases(MultiState* m, int rs, int64_t* out);
 int64_t multi_window_count(const MultiState* m, int rs, int mate);
 int64_t multi_window_records(MultiState* m, int rs, int mate, const int32_t* sub, int32_t len, gaml_aligment* out, int64_t cap);
 int64_t multi_align_window(MultiState* m, int rs, int mate, const int32_t* sub, int32_t len);
+int multi_advice_build(MultiState* m, int rs, int32_t threshold);
+int64_t multi_advice_index(MultiState* m, int rs, int64_t* offs, int32_t* ent, int64_t cap);
+int64_t multi_advice_candidates(MultiState* m, int rs, const int32_t* path, int32_t n, const int32_t* reach, int32_t n_reach, int32_t flags,
+                                int32_t* out, int64_t cap);
 int multi_compact_tables(MultiState* m);
 int multi_sync(MultiState* m);
 int multi_set_event_timing(MultiState* m, int on);

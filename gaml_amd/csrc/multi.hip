@@ -731,6 +731,32 @@ int64_t multi_align_window(MultiState* m, int rs, int mate, const int32_t* sub, 
   for (int64_t v : cnt) total += v;
   return total;
 }
+// the advice move: every shard registers and aligns the windows like the others and serves its own pairs; shards hold
+// contiguous pair ranges in rank order, so their parts one after the other are the whole set's
+int multi_advice_build(MultiState* m, int rs, int32_t threshold) {
+  return m->run_all([=](int, gaml_hip_ctx* kid) { return ctx_advice_build(kid, rs, threshold); });
+}
+int64_t multi_advice_index(MultiState* m, int rs, int64_t* offs, int32_t* ent, int64_t cap) {
+  std::vector<std::vector<int64_t>> o((size_t)m->n());
+  std::vector<std::vector<int32_t>> e((size_t)m->n());
+  if (int rc = m->run_all([&](int k, gaml_hip_ctx* kid) { return ctx_advice_index(kid, rs, o[k], e[k]); })) return rc;
+  int64_t r = 0, at = 0;
+  for (int k = 0; k < m->n(); k++) {
+    for (size_t i = 0; i + 1 < o[k].size(); i++, r++) if (offs) offs[r] = at + o[k][i];
+    for (int32_t x : e[k]) { if (ent && at < cap) ent[at] = x; at++; }
+  }
+  if (offs) offs[r] = at;
+  return at;
+}
+int64_t multi_advice_candidates(MultiState* m, int rs, const int32_t* path, int32_t n, const int32_t* reach, int32_t n_reach, int32_t flags,
+                                int32_t* out, int64_t cap) {
+  std::vector<const std::vector<int32_t>*> part((size_t)m->n(), nullptr);
+  if (int rc = m->run_all([&](int k, gaml_hip_ctx* kid) { return ctx_advice_candidates(kid, rs, path, n, reach, n_reach, flags, &part[k]); })) return rc;
+  int64_t at = 0;
+  for (const std::vector<int32_t>* p : part)
+    for (int32_t x : *p) { if (out && at < cap) out[at] = x; at++; }
+  return at;
+}
 int multi_compact_tables(MultiState* m) { for (gaml_hip_ctx* kid : m->kids) gaml_hip_compact_tables(kid); return GAML_HIP_OK; }
 int multi_sync(MultiState* m) { return m->run_all([](int, gaml_hip_ctx* kid) { return gaml_hip_sync(kid); }); }
 int multi_set_event_timing(MultiState* m, int on) { return m->run_all([on](int, gaml_hip_ctx* kid) { return gaml_hip_set_event_timing(kid, on); }); }
@@ -772,6 +798,7 @@ int gaml_hip_create_multi(gaml_hip_ctx** out, const int32_t* devices, int32_t n_
     gaml_hip_ctx* kid = nullptr;
     rc = gaml_hip_create(&kid, devices[i]);
     if (rc == GAML_HIP_OK) rc = gaml_hip_set_shard(kid, i, n_devices);
+    if (rc == GAML_HIP_OK) ctx_set_multi_shard(kid);
     if (kid) { m->kids.push_back(kid); m->devices.push_back(devices[i]); }
   }
   if (rc != GAML_HIP_OK) {

@@ -201,6 +201,30 @@ class ProbCalculator {
   }
   double CalcProb(vector<vector<int>>& paths, int& total_len) { vector<pair<int, int>> zeros; return CalcProb(paths, zeros, total_len); }
   double CalcProb(vector<vector<int>>& paths) { int tl; return CalcProb(paths, tl); }
+  // the advice move of a paired library (ExtendPathsAdv moves.cc:948-986): as include/gaml_hip_prob_calculator.h
+  bool AdviceCandidates(ReadSet& rs1, ReadSet& rs2, int threshold, const vector<int>& path, bool only_out, bool allow_gaps,
+                        const vector<int>& reach, vector<int>& cands) {
+    if (!ctx_ && !Build()) { fprintf(stderr, "gaml_hip: %s\n", err_.c_str()); exit(1); }
+    int h = -1;  // Build() adds the single sets first, then the paired ones: handles count every set in creation order
+    for (size_t i = 0; i < paired_reads.size(); i++)
+      if (paired_reads[i].second.first == &rs1 && paired_reads[i].second.second == &rs2) h = (int)(single_reads.size() + i);
+    if (h < 0) return false;
+    auto die = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, gaml_hip_last_error(ctx_)); exit(1); };
+    if (gaml_hip_advice_build(ctx_, h, threshold) != GAML_HIP_OK) die("gaml_hip_advice_build");
+    const int32_t flags = (only_out ? GAML_HIP_ADVICE_ONLY_OUT : 0) | (allow_gaps ? GAML_HIP_ADVICE_ALLOW_GAPS : 0);
+    vector<int32_t> p(path.begin(), path.end()), r(reach.begin(), reach.end());
+    int32_t none = 0;
+    if (advice_buf_.empty()) advice_buf_.resize(1 << 14);
+    auto query = [&]() {
+      return gaml_hip_advice_candidates(ctx_, h, p.empty() ? &none : p.data(), (int32_t)p.size(), r.empty() ? &none : r.data(),
+                                        (int32_t)r.size(), flags, advice_buf_.data(), (int64_t)advice_buf_.size());
+    };
+    int64_t n = query();
+    if (n > (int64_t)advice_buf_.size()) { advice_buf_.resize((size_t)n); n = query(); }  // the same call again: the same list
+    if (n < 0) die("gaml_hip_advice_candidates");
+    cands.assign(advice_buf_.begin(), advice_buf_.begin() + n);
+    return true;
+  }
 
   vector<pair<SingleReadConfig, ReadSet*>> single_reads;
   vector<pair<PairedReadConfig, pair<ReadSet*, ReadSet*>>> paired_reads;
@@ -313,6 +337,7 @@ class ProbCalculator {
   gaml_hip_ctx* ctx_ = nullptr;
   int device_;
   string err_;
+  vector<int32_t> advice_buf_;  // AdviceCandidates: kept from call to call, so that one call fetches the list
 };
 
 // walks file as the reference writes it (Graph::OutputPathC graph.cc:277-291):

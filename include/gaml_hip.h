@@ -307,6 +307,27 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* ctx, int32_t n_sets, const int32_t* p
                              const int32_t* set_offs, double* probs_out, int32_t* zeros_out, int32_t* total_lens_out);
 
 
+/* ---- the advice move of a paired set (ExtendPathsAdv moves.cc:933-998) -------------------------------------------
+ * gaml_hip_advice_build: ReadSet::BuildAdviceIndex (graph.cc:323-342) on mate 2 -- registers (and aligns) the one-node
+ *   window of every node longer than `threshold` and inverts their records into a per-pair list of nodes. Runs once per
+ *   read set: a later call with another threshold does nothing. Paired sets only (else GAML_HIP_EINVAL).
+ * gaml_hip_advice_index: that index; pair r's entries are entries[offs[r] .. offs[r+1]), each node << 1 | orient1
+ *   (orient1: the pair's first record in the node's window has orientation 1, i.e. the node is in GetAdviceIndex1),
+ *   nodes ascending. offs: n_pairs + 1; writes at most `cap` entries, returns their total (GAML_HIP_ESTATE: not built).
+ * gaml_hip_advice_candidates: `cands` of moves.cc:956-986 for a path the caller has already reversed if it wanted to:
+ *   registers the mate-1 windows GetSubpathsFromPath names (rs1.GetPositions graph.cc:651-712), keeps the pairs whose
+ *   first slot has orientation 0, and lists their GetAdviceIndex1 nodes that pass `flags` -- ONLY_OUT: skip nodes of the
+ *   path and their twins; ALLOW_GAPS: keep every node, else only those in `reach` (the keys of reach_limit_[path.back()]).
+ *   Pairs ascending, duplicates kept: the list equals the reference's element for element. Writes at most `cap` entries,
+ *   returns the count. The retry with ALLOW_GAPS on an empty list (moves.cc:975-987) is the caller's.
+ * Single-device, in-process multi-device and host-only contexts; rank-per-process contexts get GAML_HIP_ESTATE. */
+#define GAML_HIP_ADVICE_ONLY_OUT 1
+#define GAML_HIP_ADVICE_ALLOW_GAPS 2
+int gaml_hip_advice_build(gaml_hip_ctx* ctx, int readset, int32_t threshold);
+int64_t gaml_hip_advice_index(gaml_hip_ctx* ctx, int readset, int64_t* offs /* n_pairs + 1 */, int32_t* entries, int64_t cap);
+int64_t gaml_hip_advice_candidates(gaml_hip_ctx* ctx, int readset, const int32_t* path, int32_t path_len, const int32_t* reach,
+                                   int32_t n_reach, int32_t flags, int32_t* out, int64_t cap);
+
 /* ---- introspection (tests, bench, logging) ----------------------------------------- */
 int gaml_hip_num_readsets(const gaml_hip_ctx* ctx);
 int gaml_hip_readset_kind(const gaml_hip_ctx* ctx, int readset);   /* 0 single, 1 paired, 2 pacbio */

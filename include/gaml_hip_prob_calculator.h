@@ -101,6 +101,35 @@ class ProbCalculator {
     return CalcProb(paths, tl);
   }
 
+  // The advice move of a paired library (ExtendPathsAdv moves.cc:948-986; the moves.cc patch is INTEGRATION.md §7):
+  // `cands` as the reference builds it from rs2's advice index and rs1.GetPositions(gr, path), element for element,
+  // for a path the caller has already reversed if it wanted to. `reach`: the keys of gr.reach_limit_[path.back()].
+  // The index is built on first use (BuildAdviceIndex graph.cc:323-342: the first threshold stays); the windows these
+  // calls register are scored like any other, as in the reference. false: (rs1, rs2) is not one of paired_reads.
+  bool AdviceCandidates(ReadSet& rs1, ReadSet& rs2, int threshold, const vector<int>& path, bool only_out, bool allow_gaps,
+                        const vector<int>& reach, vector<int>& cands) {
+    if (!ctx_) Build();
+    int h = -1;  // Build() adds the single sets first, then the paired ones: handles count every set in creation order
+    for (size_t i = 0; i < paired_reads.size(); i++)
+      if (paired_reads[i].second.first == &rs1 && paired_reads[i].second.second == &rs2) h = (int)(single_reads.size() + i);
+    if (h < 0) return false;
+    if (gaml_hip_advice_build(ctx_, h, threshold) != GAML_HIP_OK) Die("gaml_hip_advice_build");
+    const int32_t flags = (only_out ? GAML_HIP_ADVICE_ONLY_OUT : 0) | (allow_gaps ? GAML_HIP_ADVICE_ALLOW_GAPS : 0);
+    vector<int32_t> p(path.begin(), path.end()), r(reach.begin(), reach.end());
+    int32_t none = 0;
+    if (advice_buf_.empty()) advice_buf_.resize(1 << 14);
+    int64_t n = gaml_hip_advice_candidates(ctx_, h, p.empty() ? &none : &p[0], (int32_t)p.size(), r.empty() ? &none : &r[0],
+                                           (int32_t)r.size(), flags, &advice_buf_[0], (int64_t)advice_buf_.size());
+    if (n > (int64_t)advice_buf_.size()) {  // longer than any list so far: the same call again returns the same list
+      advice_buf_.resize((size_t)n);
+      n = gaml_hip_advice_candidates(ctx_, h, p.empty() ? &none : &p[0], (int32_t)p.size(), r.empty() ? &none : &r[0],
+                                     (int32_t)r.size(), flags, &advice_buf_[0], (int64_t)advice_buf_.size());
+    }
+    if (n < 0) Die("gaml_hip_advice_candidates");
+    cands.assign(advice_buf_.begin(), advice_buf_.begin() + n);
+    return true;
+  }
+
   vector<pair<SingleReadConfig, ReadSet*>> single_reads;
   vector<pair<PairedReadConfig, pair<ReadSet*, ReadSet*>>> paired_reads;
   vector<pair<SingleReadConfig, PacbioReadSet*>> pacbio_reads;
@@ -215,6 +244,7 @@ class ProbCalculator {
   }
   vector<int> pacbio_handles_;
   gaml_hip_ctx* ctx_;
+  vector<int32_t> advice_buf_;  // AdviceCandidates: kept from call to call, so that one call fetches the list
 };
 
 #endif
