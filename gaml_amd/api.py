@@ -229,6 +229,11 @@ def _load():
         L.gaml_hip_advice_index.restype = C.c_int64
         L.gaml_hip_advice_candidates.argtypes = [vp, C.c_int, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
         L.gaml_hip_advice_candidates.restype = C.c_int64
+    if hasattr(L, "gaml_hip_gap_profile"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_gap_profile.argtypes = [vp, _i32p, _i64p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gaml_hip_fix_gap_length.argtypes = [vp, _i32p, _i64p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.POINTER(C.c_int32)]
+        L.gaml_hip_gap_stats.argtypes = [vp, _i64p]
     if hasattr(L, "gaml_hip_debug_timeline"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_debug_timeline.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64]
     L.gaml_hip_last_phases.argtypes = [vp, _f64p]
@@ -538,6 +543,39 @@ class Context:
         self._check(_lib.gaml_hip_calc_prob_batch(self._h, b.n_sets, b.flat, b.offs, b.set_offs, probs, zeros.ctypes.data, tls.ctypes.data))
         z = zeros.reshape(-1, ns, 2)[:, : self.num_readsets()]
         return [(float(probs[i]), z[i].copy(), int(tls[i])) for i in range(b.n_sets)]
+
+    def gap_profile(self, paths, path_id, gap_pos, lens):
+        """[(prob, zeros, total_len)] of `paths` with entry gap_pos of path path_id set to -l for every l of lens
+        (gaml_hip_gap_profile): the set is planned once, the lengths are scored eight to a pass over the records."""
+        flat, offs = _flat(paths)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        n = int(lens.size)
+        ns = max(1, self.num_readsets())
+        probs = np.zeros(max(1, n))
+        zeros = np.zeros(max(1, n) * 2 * ns, np.int32)
+        tls = np.zeros(max(1, n), np.int32)
+        self._check(_lib.gaml_hip_gap_profile(self._h, flat, offs, len(paths), path_id, gap_pos, lens.ctypes.data if n else None, n,
+                                              probs.ctypes.data, zeros.ctypes.data, tls.ctypes.data))
+        z = zeros.reshape(-1, ns, 2)[:, : self.num_readsets()]
+        return [(float(probs[i]), z[i].copy(), int(tls[i])) for i in range(n)]
+
+    def fix_gap_length(self, paths, path_id, gap_pos, trace_cap=4096):
+        """(length, trace) of the reference's FixGapLength (moves.cc:694-800) on the gap at paths[path_id][gap_pos]: the
+        length it leaves there and its evaluations [(length, value)] in its order (gaml_hip_fix_gap_length)."""
+        flat, offs = _flat(paths)
+        out, n = C.c_int32(), C.c_int32()
+        tl = np.zeros(max(1, trace_cap), np.int32)
+        tp = np.zeros(max(1, trace_cap))
+        self._check(_lib.gaml_hip_fix_gap_length(self._h, flat, offs, len(paths), path_id, gap_pos, C.byref(out), tl.ctypes.data, tp.ctypes.data,
+                                                 trace_cap, C.byref(n)))
+        k = min(n.value, trace_cap)
+        return out.value, [(int(tl[i]), float(tp[i])) for i in range(k)]
+
+    def gap_stats(self):
+        """{calls, device_lengths, fallback_lengths, device_passes} of the gap profiles so far (gaml_hip_gap_stats)."""
+        out = np.zeros(4, np.int64)
+        self._check(_lib.gaml_hip_gap_stats(self._h, out))
+        return dict(zip(("calls", "device_lengths", "fallback_lengths", "device_passes"), (int(x) for x in out)))
 
     def calc_partials(self, paths):
         flat, offs = _flat(paths)

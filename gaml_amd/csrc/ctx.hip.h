@@ -496,6 +496,11 @@ struct gaml_hip_ctx {
   hipStream_t fetch_stream = nullptr;
   DevBuf batch_dev;  // gaml_hip_calc_prob_batch: 4 doubles per read set and path set
   PinBuf batch_host;
+  // gaml_hip_gap_profile / gaml_hip_fix_gap_length (gap_profile.hip.h): {profile calls, lengths scored on the device route, on the
+  // fallback, device passes}, and the path set with the base length in its gap (kept from call to call)
+  int64_t gap_stats[4] = {0, 0, 0, 0};
+  std::vector<int32_t> gap_flat;
+  std::vector<int64_t> gap_offs;
   // evaluation in progress (between eval_begin and eval_finish)
   bool pending_open = false;
   std::vector<Walk> pending_paths;

@@ -1497,3 +1497,4 @@ int gaml_hip_kernel_stats(gaml_hip_ctx* c, int reset, int64_t* launches, double*
 }  // extern "C"
 
 #include "advice.hip.h"
+#include "gap_profile.hip.h"

@@ -226,6 +226,20 @@ class ProbCalculator {
     return true;
   }
 
+  // the gap-length search (FixGapLength moves.cc:729-800): as include/gaml_hip_prob_calculator.h
+  bool FixGapLength(vector<vector<int>>& paths, int path_id, int gap_pos) {
+    if (!ctx_ && !Build()) { fprintf(stderr, "gaml_hip: %s\n", err_.c_str()); exit(1); }
+    if (!FillPacbioCache(paths)) { fprintf(stderr, "gaml_hip: %s\n", err_.c_str()); exit(1); }
+    vector<int32_t> flat;
+    vector<int64_t> offs(1, 0);
+    for (auto& p : paths) { flat.insert(flat.end(), p.begin(), p.end()); offs.push_back((int64_t)flat.size()); }
+    int32_t dummy = 0, len = 0;
+    int rc = gaml_hip_fix_gap_length(ctx_, flat.empty() ? &dummy : flat.data(), offs.data(), (int32_t)paths.size(), path_id, gap_pos, &len, nullptr, nullptr, 0, nullptr);
+    if (rc != GAML_HIP_OK) { fprintf(stderr, "gaml_hip_fix_gap_length: %s\n", gaml_hip_last_error(ctx_)); exit(1); }
+    paths[path_id][gap_pos] = -len;
+    return true;
+  }
+
   vector<pair<SingleReadConfig, ReadSet*>> single_reads;
   vector<pair<PairedReadConfig, pair<ReadSet*, ReadSet*>>> paired_reads;
   vector<pair<SingleReadConfig, PacbioReadSet*>> pacbio_reads;

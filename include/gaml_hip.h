@@ -328,6 +328,34 @@ int64_t gaml_hip_advice_index(gaml_hip_ctx* ctx, int readset, int64_t* offs /* n
 int64_t gaml_hip_advice_candidates(gaml_hip_ctx* ctx, int readset, const int32_t* path, int32_t path_len, const int32_t* reach,
                                    int32_t n_reach, int32_t flags, int32_t* out, int64_t cap);
 
+/* ---- the gap-length search (FixGapLength moves.cc:694-800) ----------------------------------------------------------
+ * gaml_hip_gap_profile: probs_out[k] is what gaml_hip_calc_prob returns for `paths` with entry `gap_pos` of path `path_id`
+ *   (a gap: negative) set to -lens[k]; zeros_out (n_lens * 2 * num_readsets) and total_lens_out (n_lens) may be NULL.
+ *   A gap's length changes where the windows behind it sit and 2T, nothing else: a context of paired sets without
+ *   coverage penalty on a large-BAR device plans the set once, with lens[0], derives every other length's tables from
+ *   the resident ones on the device and scores up to 8 lengths per pass over the records. Every other context (other
+ *   kinds of read sets, a penalty, no memo, several devices, rank-per-process -- there the call is collective) runs the
+ *   lengths through gaml_hip_calc_prob_batch / gaml_hip_calc_prob: same values. GAML_HIP_EINVAL: path_id or gap_pos
+ *   out of range, an entry that is not a gap, a length < 1, n_lens < 0, a total length beyond int32. n_lens == 0 does
+ *   nothing. Afterwards the library's tables describe the set with lens[0].
+ * gaml_hip_fix_gap_length: FixGapLength(paths, path_id, gap_pos, prob_calc, prev_len) -- *len_out is the length the
+ *   reference leaves in paths[path_id][gap_pos] (the caller stores -*len_out there). The trace is the reference's sequence
+ *   of CalcProb evaluations as (length, value), in its order: at most trace_cap are written, *n_trace_out (may be NULL)
+ *   is their number. The values come from gap profiles of up to 8 lengths chosen before they are needed (the first
+ *   probes with the doubling bounds, a ternary step with both possible next steps), so the search costs a few passes,
+ *   not one blocking call per evaluation; where the profile takes its fallback nothing is computed ahead.
+ *   GAML_HIP_EINVAL also when the search reaches a length whose total would not fit int32.
+ * gaml_hip_gap_stats: cumulative {profile calls (the search's included), lengths scored on the device route, lengths
+ *   scored on the fallback, device passes}. */
+int gaml_hip_gap_profile(gaml_hip_ctx* ctx, const int32_t* paths, const int64_t* path_offs, int32_t n_paths,
+                         int32_t path_id, int32_t gap_pos, const int32_t* lens, int32_t n_lens,
+                         double* probs_out, int32_t* zeros_out /* n_lens * 2 * num_readsets, may be NULL */,
+                         int32_t* total_lens_out /* may be NULL */);
+int gaml_hip_fix_gap_length(gaml_hip_ctx* ctx, const int32_t* paths, const int64_t* path_offs, int32_t n_paths,
+                            int32_t path_id, int32_t gap_pos, int32_t* len_out,
+                            int32_t* trace_lens, double* trace_probs, int32_t trace_cap, int32_t* n_trace_out);
+int gaml_hip_gap_stats(gaml_hip_ctx* ctx, int64_t* out4);
+
 /* ---- introspection (tests, bench, logging) ----------------------------------------- */
 int gaml_hip_num_readsets(const gaml_hip_ctx* ctx);
 int gaml_hip_readset_kind(const gaml_hip_ctx* ctx, int readset);   /* 0 single, 1 paired, 2 pacbio */

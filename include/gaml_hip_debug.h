@@ -63,7 +63,8 @@ int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int
  * evaluations takes over k evaluations after its start (default 96), 15 = 1: rebuilds never retire unused windows,
  * 17 = 1: whole-set calls build their occurrence tables on the host (no device route, occ_device.hip.h),
  * 16 = 1: record tables keep the records that can never survive the overwrite rule (takes effect at the next table build;
- * same values either way), 18 = d: tables are rebuilt when the delta lists pass pairs / d (default 8), 19 = 1: no static
+ * same values either way), 18 = d > 1: tables are rebuilt when the delta lists pass pairs / d (default 8), 18 = 1: gap profiles take their
+ * fallback route (gaml_hip_gap_profile; the rebuild rule stays the default), 19 = 1: no static
  * memo indices (takes effect at the next table build; same values either way), 20 = blocks of the compact class's second
  * part, 22 = 1: delta maintenance by one-block launches only (default: multi-block
  * above 3,000 records). Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */

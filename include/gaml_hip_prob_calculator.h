@@ -130,6 +130,27 @@ class ProbCalculator {
     return true;
   }
 
+  // The gap-length search (FixGapLength moves.cc:729-800 with its helper :694-727; the moves.cc patch is INTEGRATION.md §8):
+  // leaves in paths[path_id][gap_pos] what the reference leaves there, after the same sequence of evaluations -- taken
+  // from the library eight lengths to a pass (gaml_hip_fix_gap_length). Returns true, like the reference. The
+  // reference's printf lines are not kept.
+  bool FixGapLength(vector<vector<int> >& paths, int path_id, int gap_pos) {
+    if (!ctx_) Build();
+    FillPacbioCache(paths);
+    vector<int32_t> flat;
+    vector<int64_t> offs(1, 0);
+    for (size_t i = 0; i < paths.size(); i++) {
+      flat.insert(flat.end(), paths[i].begin(), paths[i].end());
+      offs.push_back((int64_t)flat.size());
+    }
+    int32_t none = 0, len = 0;
+    if (gaml_hip_fix_gap_length(ctx_, flat.empty() ? &none : &flat[0], &offs[0], (int32_t)paths.size(), path_id, gap_pos, &len, NULL, NULL, 0,
+                                NULL) != GAML_HIP_OK)
+      Die("gaml_hip_fix_gap_length");
+    paths[path_id][gap_pos] = -len;
+    return true;
+  }
+
   vector<pair<SingleReadConfig, ReadSet*>> single_reads;
   vector<pair<PairedReadConfig, pair<ReadSet*, ReadSet*>>> paired_reads;
   vector<pair<SingleReadConfig, PacbioReadSet*>> pacbio_reads;
