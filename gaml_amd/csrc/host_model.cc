@@ -1854,6 +1854,7 @@ void pacbio_dp_ops(const std::vector<std::pair<int32_t, char>>& cigar, std::vect
     for (int i = 0; i < 5; i++) if (run > top[i]) { for (int k = 4; k > i; k--) top[k] = top[k - 1]; top[i] = run; break; }
   };
   int64_t run = 0;
+  int64_t front = 0;  // the column in which the path leaves row min(row_f, 6)
   for (const auto& op : cigar) {
     const int64_t n = std::max(0, op.first);
     if (n == 0) continue;
@@ -1862,11 +1863,13 @@ void pacbio_dp_ops(const std::vector<std::pair<int32_t, char>>& cigar, std::vect
       else ops.push_back((uint32_t)(n << 2) | 1u);
       cols += n; run += n; trail += n;
       if (!seen_other) lead += n;
+      if (rows <= 6) front = cols;
     } else {
       if (run) { close_run(run); run = 0; }
       seen_other = true;
       trail = 0;
       ops.push_back((uint32_t)(n << 2) | (op.second == 'M' ? 0u : 2u));
+      if (rows < 6) front = cols + (op.second == 'M' ? std::min<int64_t>(n, 6 - rows) : 0);
       rows += n;
       if (op.second == 'M') cols += n;
     }
@@ -1879,7 +1882,11 @@ void pacbio_dp_ops(const std::vector<std::pair<int32_t, char>>& cigar, std::vect
   out.el = seen_other ? (int32_t)std::min<int64_t>(trail + 1, 200) : 0;
   // a widened row spans at most five consecutive path rows (4 steps + their insertion runs) or a clip box
   const int64_t five = 5 + top[0] + top[1] + top[2] + top[3] + top[4];
-  out.max_width = (int32_t)std::min<int64_t>(INT32_MAX, std::max<int64_t>(std::max<int64_t>(out.bl, out.el + 1), five) + 6);
+  int64_t width = std::max<int64_t>(std::max<int64_t>(out.bl, out.el + 1), five) + 6;
+  // the leading clip box keeps column 0 in rows 0..2, whose windows reach path row 6: up to seven insertion runs, the
+  // leading one among them, which the five longest need not cover
+  if (out.bl > 0) width = std::max<int64_t>(width, front + 5);
+  out.max_width = (int32_t)std::min<int64_t>(INT32_MAX, width);
 }
 
 }  // namespace gaml
