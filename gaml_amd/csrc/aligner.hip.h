@@ -11,6 +11,12 @@
 //                        0-1 BFS as a FIFO of chain heads with a per-diagonal visited bitset
 // Records leave as (window, position, edit distance, read, strand, order) and are sorted / deduplicated
 // per window on the host exactly like the host aligner does.
+//
+// The longest read the device code takes is a compile-time parameter MR of the span and extension kernels, in two
+// instantiations (AlnLim): 254 -- a 256-bit visited set per diagonal, eight bits of a queue head for the read index,
+// two staging rounds of the span string -- and 510 -- 512 bits, nine bits, three rounds, and a second level of group
+// maxima in the span stage. The host picks one per launch from the mates involved (aligner_launch.hip.h); the search
+// itself -- order of the heads, visited semantics, first seed position -- is the same code in both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,7 +29,25 @@ __device__ unsigned long long g_aln_stamp[32];  // timing builds only (aligner_s
 #endif
 constexpr int kAlnBlock = 256;
 constexpr int kAlnSeed = 15;
-constexpr int kAlnMaxRead = 254;  // visited bitset: 4 x 64 bits per diagonal
+constexpr int kAlnMaxRead = 254;   // the narrow instantiation: visited bitset of 4 x 64 bits per diagonal
+constexpr int kAlnWideRead = 510;  // the wide one: 8 x 64 bits per diagonal (MiSeq 2 x 300 and the like)
+// what depends on the longest read MR an instantiation takes
+template <int MR>
+struct AlnLim {
+  static_assert(MR == kAlnMaxRead || MR == kAlnWideRead, "visited words, head bits and staging rounds are laid out for 254 and 510");
+  static constexpr int kVisWords = (MR + 2) / 32;           // 32-bit words of a diagonal's visited set (bit = read index + 1 <= MR + 1): 8 / 16
+  static constexpr int kHeadBits = MR > 254 ? 9 : 8;        // bits of a queue head that hold r + 1 <= MR + 1
+  static constexpr int kWinSeg = MR + 18;                   // window bases a search can touch (read length + 2 x 4 diagonals + slack)
+  static constexpr int kStrBytes = kAlnBlock + MR + 2;      // a span block's slice of the window string
+  static constexpr int kStrRounds = kStrBytes / kAlnBlock;  // staging rounds of that slice (one byte per lane and round): 2 / 3
+  static constexpr int kGrpSlots = (kStrBytes + 7) / 8;     // groups of eight keys per block: 64 / 96
+  static constexpr int kGroups = (MR - 15 + 1 + 7) / 8 + 1; // whole groups of eight keys a span can hold: 31 / 63
+  static constexpr bool kTwoLevel = kGroups > 32;           // maxima of eight GROUPS as well: a span reads <= 14 keys, <= 14 groups and kSupers of those
+  static constexpr int kSupSlots = (kGrpSlots + 7) / 8;
+  static constexpr int kSupers = kGroups / 8 + 1;
+  static constexpr int kReadRounds = (MR + 63) / 64;        // small-batch extension: 64 read bytes per round, 4 / 8
+  static constexpr int kSegRounds = (2 * MR - 3 + 63) / 64; // ... and 64 window bytes per round over <= 2 MR - 3 bases: 8 / 16
+};
 
 struct AlnWindow { int32_t str_off, len, offset; };   // window string in the batch buffer; offset = trimmed prefix (graph.cc:850)
 
@@ -86,12 +110,13 @@ struct AlnMates {
 // One block's share of the sliding maximum: the chunk's slice of the window string and its scrambled codes staged in
 // LDS, then per lane (span end i = base + threadIdx.x) the span maximum m, the earliest seed attaining it p, and whether
 // the reference emits here. Returns false (block-uniform) when the block has no work.
-constexpr int kAlnGrpSlots = (kAlnBlock + kAlnMaxRead + 2 + 7) / 8;
-constexpr int kAlnGroups = (kAlnMaxRead - kAlnSeed + 1 + 7) / 8 + 1;  // whole groups of eight keys a span can hold
-struct AlnSpanLds {
-  char str[kAlnBlock + kAlnMaxRead + 2];
-  unsigned long long key[8 * kAlnGrpSlots];             // code << 32 | ~position per seed end (>= kAlnBlock + kAlnMaxRead + 2)
-  unsigned long long grp[kAlnGrpSlots];                 // maxima of aligned groups of eight keys
+template <int MR, bool = AlnLim<MR>::kTwoLevel> struct AlnSpanSup {};  // maxima of aligned groups of eight groups: wide instantiation only
+template <int MR> struct AlnSpanSup<MR, true> { unsigned long long sup[AlnLim<MR>::kSupSlots]; };
+template <int MR>
+struct AlnSpanLds : AlnSpanSup<MR> {
+  char str[AlnLim<MR>::kStrBytes];
+  unsigned long long key[8 * AlnLim<MR>::kGrpSlots];    // code << 32 | ~position per seed end (>= kAlnBlock + MR + 2)
+  unsigned long long grp[AlnLim<MR>::kGrpSlots];        // maxima of aligned groups of eight keys
   uint32_t mx[kAlnBlock];
 };
 struct AlnSpanLane { bool emit; uint32_t m; int p, i, w, strand; };
@@ -105,7 +130,8 @@ __device__ __forceinline__ int aln_span_locate(const BlkT& blk, const WinT& wins
   rel = (int)blockIdx.x - blk[lo];
   return lo;
 }
-__device__ __forceinline__ bool aln_span_front(AlnSpanLds& L, const char* wstr, const AlnWindow win, const int w, const int rel, int R, AlnSpanLane& o, char* copy = nullptr) {
+template <int MR>
+__device__ __forceinline__ bool aln_span_front(AlnSpanLds<MR>& L, const char* wstr, const AlnWindow win, const int w, const int rel, int R, AlnSpanLane& o, char* copy = nullptr) {
   const char* s = wstr + win.str_off;
   const int W = win.len;
   const int chunks = aln_span_chunks(W, R);
@@ -115,7 +141,7 @@ __device__ __forceinline__ bool aln_span_front(AlnSpanLds& L, const char* wstr, 
   // codes of the seeds ending at j in [c_lo, c_hi]: those of span base - 1 (lane 0: the predecessor of the block's first span) up to the last span's
   const int c_lo = max(base - 1 - R + kAlnSeed, kAlnSeed - 1), c_hi = min(base + kAlnSpans - 1, W - 1);
   const int s_lo = c_lo - (kAlnSeed - 1);                        // string bases [s_lo, c_hi]
-  {  // (both rounds' loads requested before the first LDS store: c_hi - s_lo < 2 * kAlnBlock)
+  if constexpr (AlnLim<MR>::kStrRounds == 2) {  // (both rounds' loads requested before the first LDS store: c_hi - s_lo < 2 * kAlnBlock)
     const int k0 = threadIdx.x, k1 = threadIdx.x + kAlnBlock, n = c_hi - s_lo;
     const char a0 = k0 <= n ? aln_wbase(s, W, strand, s_lo + k0) : '\0', a1 = k1 <= n ? aln_wbase(s, W, strand, s_lo + k1) : '\0';
     if (k0 <= n) L.str[k0] = a0;
@@ -123,6 +149,19 @@ __device__ __forceinline__ bool aln_span_front(AlnSpanLds& L, const char* wstr, 
     if (copy && strand == 0) {  // the forward chunks of a window cover its whole string (chunk 0 starts at base 0)
       if (k0 <= n) copy[win.str_off + s_lo + k0] = a0;
       if (k1 <= n) copy[win.str_off + s_lo + k1] = a1;
+    }
+  } else {  // the same in kStrRounds rounds: c_hi - s_lo <= kAlnSpans + R < kStrRounds * kAlnBlock. (Written as loops the two-round
+            // case compiles to a different schedule than the statements above; the narrow kernels keep theirs.)
+    constexpr int NR = AlnLim<MR>::kStrRounds;
+    const int n = c_hi - s_lo;
+    char a[NR];
+#pragma unroll
+    for (int u = 0; u < NR; u++) { const int k = threadIdx.x + u * kAlnBlock; a[u] = k <= n ? aln_wbase(s, W, strand, s_lo + k) : '\0'; }
+#pragma unroll
+    for (int u = 0; u < NR; u++) { const int k = threadIdx.x + u * kAlnBlock; if (k <= n) L.str[k] = a[u]; }
+    if (copy && strand == 0) {
+#pragma unroll
+      for (int u = 0; u < NR; u++) { const int k = threadIdx.x + u * kAlnBlock; if (k <= n) copy[win.str_off + s_lo + k] = a[u]; }
     }
   }
   __syncthreads();
@@ -158,12 +197,26 @@ __device__ __forceinline__ bool aln_span_front(AlnSpanLds& L, const char* wstr, 
     L.grp[threadIdx.x] = g8;
   }
   __syncthreads();
+  if constexpr (AlnLim<MR>::kTwoLevel) {  // maxima of aligned groups of eight group maxima (a dozen lanes; one more barrier, fewer loads per span)
+    const int n_grp = (n_codes + 7) >> 3;
+    if ((int)threadIdx.x * 8 < n_grp) {  // (n_grp <= kGrpSlots, so threadIdx.x < kSupSlots)
+      unsigned long long v[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) { const unsigned long long t = L.grp[threadIdx.x * 8 + u]; v[u] = (int)threadIdx.x * 8 + u < n_grp ? t : 0ull; }
+      unsigned long long g8 = 0;
+#pragma unroll
+      for (int u = 0; u < 8; u++) g8 = v[u] > g8 ? v[u] : g8;
+      L.sup[threadIdx.x] = g8;
+    }
+    __syncthreads();
+  }
   const int i = base - 1 + (int)threadIdx.x;
   unsigned long long best = 0;
   if (i < W) {
     const int xa = max(i - R + kAlnSeed, kAlnSeed - 1) - c_lo, xb = i - c_lo;  // the span's keys: [xa, xb]
     if (xa <= xb) {
       const int ga = (xa + 7) >> 3, gb = (xb + 1) >> 3;  // whole groups [ga, gb)
+      constexpr int kAlnGrpSlots = AlnLim<MR>::kGrpSlots, kAlnGroups = AlnLim<MR>::kTwoLevel ? 14 : AlnLim<MR>::kGroups;
       unsigned long long e[14], gm[kAlnGroups];
       // (every load unconditional, its index clamped, the value masked afterwards: a predicated load compiles to a branch
       // around the load with a wait of its own)
@@ -171,12 +224,32 @@ __device__ __forceinline__ bool aln_span_front(AlnSpanLds& L, const char* wstr, 
       for (int u = 0; u < 7; u++) { const int x = xa + u; const unsigned long long v = L.key[min(x, xb)]; e[u] = (x <= xb && x < 8 * ga) ? v : 0ull; }       // before the first whole group
 #pragma unroll
       for (int u = 0; u < 7; u++) { const int x = xb - u; const unsigned long long v = L.key[max(x, xa)]; e[7 + u] = (x >= xa && x >= 8 * gb) ? v : 0ull; }  // after the last (a key counted twice changes no maximum)
+      if constexpr (!AlnLim<MR>::kTwoLevel) {
 #pragma unroll
-      for (int u = 0; u < kAlnGroups; u++) { const unsigned long long v = L.grp[min(ga + u, kAlnGrpSlots - 1)]; gm[u] = ga + u < gb ? v : 0ull; }
+        for (int u = 0; u < kAlnGroups; u++) { const unsigned long long v = L.grp[min(ga + u, kAlnGrpSlots - 1)]; gm[u] = ga + u < gb ? v : 0ull; }
 #pragma unroll
-      for (int u = 0; u < 14; u++) best = e[u] > best ? e[u] : best;
+        for (int u = 0; u < 14; u++) best = e[u] > best ? e[u] : best;
 #pragma unroll
-      for (int u = 0; u < kAlnGroups; u++) best = gm[u] > best ? gm[u] : best;
+        for (int u = 0; u < kAlnGroups; u++) best = gm[u] > best ? gm[u] : best;
+      } else {
+        // whole groups [ga, gb) = <= 7 before the first whole group of groups, the whole ones [sa, sb), <= 7 after the last
+        // (sa > sb: no multiple of eight in [ga, gb], fewer than eight groups, the first loop alone covers them)
+        constexpr int kSupSlots = AlnLim<MR>::kSupSlots, kSupers = AlnLim<MR>::kSupers;
+        const int sa = (ga + 7) >> 3, sb = gb >> 3;
+        unsigned long long sm[kSupers];
+#pragma unroll
+        for (int u = 0; u < 7; u++) { const int g = ga + u; const unsigned long long v = L.grp[min(g, kAlnGrpSlots - 1)]; gm[u] = (g < gb && g < 8 * sa) ? v : 0ull; }
+#pragma unroll
+        for (int u = 0; u < 7; u++) { const int g = gb - 1 - u; const unsigned long long v = L.grp[max(g, 0)]; gm[7 + u] = (g >= ga && g >= 8 * sb) ? v : 0ull; }
+#pragma unroll
+        for (int u = 0; u < kSupers; u++) { const int q = sa + u; const unsigned long long v = L.sup[min(q, kSupSlots - 1)]; sm[u] = q < sb ? v : 0ull; }
+#pragma unroll
+        for (int u = 0; u < 14; u++) best = e[u] > best ? e[u] : best;
+#pragma unroll
+        for (int u = 0; u < 14; u++) best = gm[u] > best ? gm[u] : best;
+#pragma unroll
+        for (int u = 0; u < kSupers; u++) best = sm[u] > best ? sm[u] : best;
+      }
     }
   }
   const uint32_t m = (uint32_t)(best >> 32);
@@ -190,16 +263,17 @@ __device__ __forceinline__ bool aln_span_front(AlnSpanLds& L, const char* wstr, 
   return true;
 }
 
+template <int MR>
 __global__ __launch_bounds__(kAlnBlock) void span_maxima_kernel(const char* wstr, const AlnWindow* wins, int n_win, int R, const int* blk,
                                                                AlnSpan* spans, unsigned* n_spans, unsigned cap_spans) {
-  __shared__ AlnSpanLds L;
+  __shared__ AlnSpanLds<MR> L;
   __shared__ int sh_wave[kAlnBlock / 64];
   __shared__ unsigned sh_base;
   AlnSpanLane o;
   AlnWindow win;
   int rel;
   const int w = aln_span_locate(blk, wins, n_win, win, rel);
-  if (!aln_span_front(L, wstr, win, w, rel, R, o)) return;
+  if (!aln_span_front<MR>(L, wstr, win, w, rel, R, o)) return;
   // ordered compaction inside the block: ballots per wave, wave totals through LDS
   const unsigned long long bal = __ballot(o.emit);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -242,7 +316,7 @@ __global__ __launch_bounds__(kAlnBlock) void candidates_kernel(const AlnSpan* sp
 //    bases match and the next cell is unvisited (the reference pushes such a step to the FRONT of its
 //    deque, so it is popped next); at the first mismatch it appends its <= 3 successors at cost + 1.
 //    Heads leave the FIFO in non-decreasing cost; cost > 3 ends the search. Visited cells: one
-//    256-bit set per diagonal shift in [-4, 4].
+//    256-bit set (512 bits in the wide instantiation) per diagonal shift in [-4, 4].
 // ---------------------------------------------------------------------------------------------
 // One WAVE per candidate. A single lane running the search serially spends ~0.5 us per visited
 // cell (dependent LDS / memory operations of a lone wave), i.e. ~0.3 ms per launch whatever the batch
@@ -251,18 +325,19 @@ __global__ __launch_bounds__(kAlnBlock) void candidates_kernel(const AlnSpan* sp
 // stops and why), marks the run in the visited set with a handful of word operations, and only the
 // bookkeeping at a mismatch (<= 3 successors) is scalar. Same states, same order, same visited
 // semantics as the FIFO-of-chain-heads search above, so the same records.
-constexpr int kAlnQueue = 128;                 // heads: r+1 (8 bits) | diag+4 (4 bits) | cost (3 bits)
-constexpr int kAlnWinSeg = kAlnMaxRead + 18;   // window bases a search can touch (read length + 2 x 4 diagonals + slack)
+constexpr int kAlnQueue = 128;                 // heads: r+1 (8 or 9 bits: AlnLim::kHeadBits) | diag+4 (4 bits) | cost (3 bits); a search makes <= 1 + 3 + 9 + 27 + 81 of them
 constexpr int kAlnWaves = 4;                   // candidates per block
-template <int WS>
+template <int MR, int WS>
 struct AlnWaveLdsT {
-  unsigned char rd[kAlnMaxRead + 2];           // the read as aligned (strand applied)
+  static constexpr int kMaxRead = MR;
+  unsigned char rd[MR + 2];                    // the read as aligned (strand applied)
   unsigned char ws[WS];                        // window segment, 0 beyond the window's end
   unsigned char seed[16];
-  uint32_t vis[9 * 8];                         // 256-bit visited set per diagonal shift in [-4, 4]; bit = read index + 1
+  uint32_t vis[9 * AlnLim<MR>::kVisWords];     // 256- or 512-bit visited set per diagonal shift in [-4, 4]; bit = read index + 1
   unsigned short q[kAlnQueue];
 };
-using AlnWaveLds = AlnWaveLdsT<kAlnWinSeg + 2>;
+template <int MR>
+using AlnWaveLds = AlnWaveLdsT<MR, AlnLim<MR>::kWinSeg + 2>;
 
 __device__ __forceinline__ void aln_lds_sync() {  // LDS traffic of ONE wave: in order in hardware, keep the compiler from reordering
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -272,21 +347,23 @@ __device__ __forceinline__ void aln_lds_sync() {  // LDS traffic of ONE wave: in
 
 template <class Lds>
 struct AlnWaveSearch {
+  static constexpr int kMaxRead = Lds::kMaxRead;
+  static constexpr int VW = AlnLim<kMaxRead>::kVisWords, HB = AlnLim<kMaxRead>::kHeadBits;  // words per diagonal, bits of r + 1 in a head
   Lds& L;
   const int lane;
   int qn;
   __device__ __forceinline__ AlnWaveSearch(Lds& l, int ln) : L(l), lane(ln), qn(0) {}
   __device__ __forceinline__ void reset() {
     qn = 0;
-    L.vis[lane] = 0;
-    if (lane < 8) L.vis[64 + lane] = 0;
+#pragma unroll
+    for (int k = 0; k < 9 * VW; k += 64) { if (k + 64 <= 9 * VW || lane < 9 * VW - k) L.vis[k + lane] = 0; }
     aln_lds_sync();
   }
   // wave-uniform arguments: true if (diag, r) was unvisited (then it is marked)
   __device__ __forceinline__ bool mark(int diag, int r) {
     const int b = r + 1;
     const uint32_t m = 1u << (b & 31);
-    const int w = (diag + 4) * 8 + (b >> 5);
+    const int w = (diag + 4) * VW + (b >> 5);
     const uint32_t old = L.vis[w];
     if (old & m) return false;
     if (lane == 0) L.vis[w] = old | m;
@@ -295,23 +372,23 @@ struct AlnWaveSearch {
   }
   __device__ __forceinline__ void push(int d, int diag, int r) {
     if (qn < kAlnQueue) {
-      if (lane == 0) L.q[qn] = (unsigned short)((r + 1) | ((diag + 4) << 8) | (d << 12));
+      if (lane == 0) L.q[qn] = (unsigned short)((r + 1) | ((diag + 4) << HB) | (d << (HB + 4)));
       qn++;
     }
   }
   __device__ __forceinline__ bool visited(int diag, int r) const {  // per-lane r
     const int b = r + 1;
-    return (L.vis[(diag + 4) * 8 + (b >> 5)] >> (b & 31)) & 1u;
+    return (L.vis[(diag + 4) * VW + (b >> 5)] >> (b & 31)) & 1u;
   }
-  // mark read indices [r_lo, r_hi] (inclusive) of one diagonal: lanes 0..7 own one word each
+  // mark read indices [r_lo, r_hi] (inclusive) of one diagonal: lanes 0..VW-1 own one word each
   __device__ __forceinline__ void mark_range(int diag, int r_lo, int r_hi) {
-    if (lane < 8 && r_hi >= r_lo) {
+    if (lane < VW && r_hi >= r_lo) {
       const int lo = r_lo + 1, hi = r_hi + 1;  // bit range, inclusive
       const int w0 = 32 * lane;
       const int a = max(lo, w0), b = min(hi, w0 + 31);
       if (a <= b) {
         const uint32_t m = (b - a == 31 ? 0xffffffffu : ((1u << (b - a + 1)) - 1u)) << (a - w0);
-        L.vis[(diag + 4) * 8 + lane] |= m;
+        L.vis[(diag + 4) * VW + lane] |= m;
       }
     }
     aln_lds_sync();
@@ -323,16 +400,16 @@ struct AlnWaveSearch {
   // visited set: the successors' bits never lie inside the run's range. Returns bit 0 / 1 / 2 = S / W / R was unvisited.
   __device__ __forceinline__ unsigned finish_run(int diag, int r_lo, int r_hi, bool succ, bool sw, int rs, int dw, int rw, int dr, int rr) {
     const int bs = rs + 1, bw = rw + 1, br = rr + 1;
-    const int iw = (dw + 4) * 8 + (bw >> 5), ir = (dr + 4) * 8 + (br >> 5);
+    const int iw = (dw + 4) * VW + (bw >> 5), ir = (dr + 4) * VW + (br >> 5);
     uint32_t own = 0, ww = ~0u, wr = ~0u;
-    if (lane < 8) own = L.vis[(diag + 4) * 8 + lane];
+    if (lane < VW) own = L.vis[(diag + 4) * VW + lane];
     if (succ) { if (sw) ww = L.vis[iw]; wr = L.vis[ir]; }
     // S lives in one of the run's own words (lane bs >> 5)
-    const uint32_t s_word = (uint32_t)__builtin_amdgcn_readlane((int)own, __builtin_amdgcn_readfirstlane(bs >> 5) & 7);
+    const uint32_t s_word = (uint32_t)__builtin_amdgcn_readlane((int)own, __builtin_amdgcn_readfirstlane(bs >> 5) & (VW - 1));
     const bool s_new = succ && sw && !((s_word >> (bs & 31)) & 1u);
     const bool w_new = succ && sw && !((ww >> (bw & 31)) & 1u);
     const bool r_new = succ && !((wr >> (br & 31)) & 1u);
-    if (lane < 8) {
+    if (lane < VW) {
       uint32_t m = 0;
       if (r_hi >= r_lo) {
         const int lo = r_lo + 1, hi = r_hi + 1, w0 = 32 * lane;  // bit range, inclusive
@@ -340,7 +417,7 @@ struct AlnWaveSearch {
         if (a <= b) m = (b - a == 31 ? 0xffffffffu : ((1u << (b - a + 1)) - 1u)) << (a - w0);
       }
       if (s_new && lane == (bs >> 5)) m |= 1u << (bs & 31);
-      if (m) L.vis[(diag + 4) * 8 + lane] = own | m;
+      if (m) L.vis[(diag + 4) * VW + lane] = own | m;
     }
     if (lane == 0) {
       if (w_new) L.vis[iw] = ww | (1u << (bw & 31));
@@ -356,8 +433,8 @@ struct AlnWaveSearch {
     aln_lds_sync();
     for (int qi = 0; qi < qn; qi++) {
       const uint32_t e = L.q[qi];
-      const int d = (int)(e >> 12), diag = (int)((e >> 8) & 15) - 4;
-      int r = (int)(e & 255) - 1;
+      const int d = (int)(e >> (HB + 4)), diag = (int)((e >> HB) & 15) - 4;
+      int r = (int)(e & ((1u << HB) - 1u)) - 1;
       int g = win_pos + (r - read_pos) + diag;
       if (d > 3) return -1;
       while (true) {
@@ -366,8 +443,8 @@ struct AlnWaveSearch {
         const bool at_end = rr == R;
         // (the three LDS reads unconditional and side by side, indices clamped; `||` chains compile to a branch per load)
         const bool in_read = rr < R;
-        const unsigned char wb = wbase(gg), rb = L.rd[min(rr, kAlnMaxRead)];
-        const bool seen = visited(diag, min(rr, kAlnMaxRead) + 1);
+        const unsigned char wb = wbase(gg), rb = L.rd[min(rr, kMaxRead)];
+        const bool seen = visited(diag, min(rr, kMaxRead) + 1);
         const bool may_advance = (gg + 1 < W) | (rr + 1 == R);
         const bool mism = in_read & (wb != rb);
         const bool stop = at_end | (in_read & ((wb != rb) | !may_advance | seen));
@@ -404,8 +481,8 @@ struct AlnWaveSearch {
     aln_lds_sync();
     for (int qi = 0; qi < qn; qi++) {
       const uint32_t e = L.q[qi];
-      const int d = (int)(e >> 12), diag = (int)((e >> 8) & 15) - 4;
-      int r = (int)(e & 255) - 1;
+      const int d = (int)(e >> (HB + 4)), diag = (int)((e >> HB) & 15) - 4;
+      int r = (int)(e & ((1u << HB) - 1u)) - 1;
       int g = win_pos + (r - read_pos) + diag;
       if (d > 3) return -1;
       while (true) {
@@ -443,7 +520,8 @@ struct AlnWaveSearch {
 };
 
 // one candidate, one wave (every `return` leaves the candidate, not the kernel)
-__device__ __forceinline__ void extend_candidate(AlnWaveLds& L, const int lane, const unsigned t, const AlnCand* cands, const char* wstr,
+template <int MR>
+__device__ __forceinline__ void extend_candidate(AlnWaveLds<MR>& L, const int lane, const unsigned t, const AlnCand* cands, const char* wstr,
                                                  const AlnWindow* wins, const char* reads, const int64_t* read_off, AlnHit* hits) {
   const AlnCand c = cands[t];
   AlnHit out{c.win, 0, -1, c.read, c.strand, c.order};
@@ -452,7 +530,8 @@ __device__ __forceinline__ void extend_candidate(AlnWaveLds& L, const int lane, 
   const int W = win.len;
   const char* rd = reads + read_off[c.read];
   const int R = (int)(read_off[c.read + 1] - read_off[c.read]);
-  if (R > kAlnMaxRead || R < kAlnSeed) { if (lane == 0) hits[t] = out; return; }
+  constexpr int kAlnWinSeg = AlnLim<MR>::kWinSeg;
+  if (R > MR || R < kAlnSeed) { if (lane == 0) hits[t] = out; return; }
   // seed start in the forward window string (graph.cc:866-872)
   const int win_pos = c.strand == 0 ? c.seed_end - kAlnSeed + 1 : W - (c.seed_end + 1);
   // the read as aligned: strand 1 = reverse complement of the stored read (graph.cc:873-876); coalesced
@@ -469,7 +548,7 @@ __device__ __forceinline__ void extend_candidate(AlnWaveLds& L, const int lane, 
     const int i = base + lane;
     bool same = i + kAlnSeed <= R;
 #pragma unroll
-    for (int k = 0; k < kAlnSeed; k++) same = same & (L.rd[min(i + k, kAlnMaxRead)] == L.seed[k]);
+    for (int k = 0; k < kAlnSeed; k++) same = same & (L.rd[min(i + k, MR)] == L.seed[k]);
     const unsigned long long hit = __ballot(same);
     if (hit) read_pos = base + (__ffsll((long long)hit) - 1);
   }
@@ -480,7 +559,7 @@ __device__ __forceinline__ void extend_candidate(AlnWaveLds& L, const int lane, 
   for (int b = lane; b < seg; b += 64) L.ws[b] = (unsigned char)(g0 + b < W ? ws[g0 + b] : '\0');  // the reference reads the terminator at g == W
   aln_lds_sync();
   auto wbase = [&](int g) -> unsigned char { const int i = g - g0; const unsigned char v = L.ws[min(max(i, 0), kAlnWinSeg)]; return (i >= 0 && i < seg) ? v : (unsigned char)'\0'; };
-  AlnWaveSearch<AlnWaveLds> S(L, lane);
+  AlnWaveSearch<AlnWaveLds<MR>> S(L, lane);
   const int fwd = S.forward(wbase, R, W, win_pos, read_pos);
   if (fwd < 0) { if (lane == 0) hits[t] = out; return; }
   int begin_pos = -1;
@@ -492,15 +571,16 @@ __device__ __forceinline__ void extend_candidate(AlnWaveLds& L, const int lane, 
 }
 
 // grid-stride over the candidates: the grid does not depend on their number, so the launch needs no count on the host
+template <int MR>
 __global__ __launch_bounds__(64 * kAlnWaves) void extend_kernel(const AlnCand* cands, const unsigned* n_cands, unsigned cap_cands,
                                                                 const char* wstr, const AlnWindow* wins, const char* reads,
                                                                 const int64_t* read_off, AlnHit* hits) {
-  __shared__ AlnWaveLds lds_all[kAlnWaves];
+  __shared__ AlnWaveLds<MR> lds_all[kAlnWaves];
   const unsigned n = *n_cands < cap_cands ? *n_cands : cap_cands;
   const int lane = (int)(threadIdx.x & 63);
-  AlnWaveLds& L = lds_all[threadIdx.x >> 6];
+  AlnWaveLds<MR>& L = lds_all[threadIdx.x >> 6];
   for (unsigned t = blockIdx.x * kAlnWaves + (threadIdx.x >> 6); t < n; t += gridDim.x * kAlnWaves) {  // whole waves move together
-    extend_candidate(L, lane, t, cands, wstr, wins, reads, read_off, hits);
+    extend_candidate<MR>(L, lane, t, cands, wstr, wins, reads, read_off, hits);
     aln_lds_sync();  // the wave's LDS slice is reused by its next candidate
   }
 }

@@ -4,9 +4,18 @@
 
 // ---------------------------------------------------------------------------------------
 // GPU window alignment of every pending window of one mate (cold path). Falls back to the host
-// aligner for inputs the kernels do not cover (reads shorter than 16 or longer than 254 bases,
+// aligner for inputs the kernels do not cover (reads shorter than 16 or longer than 510 bases,
 // mixed read lengths are fine). Records are identical to the host aligner's.
+// The span and extension kernels exist in two instantiations (AlnLim, aligner.hip.h): reads up to 254 bases and up to
+// 510. A launch takes the wide one only where it has to: the general route and the per-mate small batches launch per
+// mate, so a mate whose longest read has <= 254 bases keeps the narrow kernels whatever the other mate holds; the
+// paired small-batch pipeline runs both mates in one kernel and is wide if either mate is. The fixed capacities of the
+// small-batch pipeline (kFastSpans, kFastCands, the 256 KiB input block and window copy, kAlnArgStr, kAlnArgWins) count
+// spans, candidates, windows and window bytes, not read bases: longer reads mean longer junction windows, so fewer of
+// them fit, and a batch that does not fit falls to the general route as before -- nothing is truncated.
 // ---------------------------------------------------------------------------------------
+#define ALN_LAUNCH(wide, K, ...) do { if (wide) hipLaunchKernelGGL((K<kAlnWideRead>), __VA_ARGS__); else hipLaunchKernelGGL((K<kAlnMaxRead>), __VA_ARGS__); } while (0)
+#define ALN_EXT_LAUNCH(wide, K, ...) do { if (wide) hipExtLaunchKernelGGL((K<kAlnWideRead>), __VA_ARGS__); else hipExtLaunchKernelGGL((K<kAlnMaxRead>), __VA_ARGS__); } while (0)
 // Small batches -- what an annealing move brings: a handful of new junction windows, a few thousand seed candidates.
 // Everything on the library's stream, ONE wait: the window strings and descriptors are written by the host straight
 // into device memory (large BAR) or copied asynchronously from pinned memory; the three kernels run back to back (the
@@ -86,8 +95,11 @@ int aln_small_reserve(gaml_hip_ctx* c, AlignSmall& S) {
 }
 
 bool aln_gpu_capable(const gaml_hip_ctx* c, const ShortMate& m) {
-  return !(c->device < 0 || KNOB(c, 5) == 1 || m.index_read_len < 16 || m.max_len > kAlnMaxRead || m.n_local() == 0 || m.bucket_hash.empty());
+  return !(c->device < 0 || KNOB(c, 5) == 1 || m.index_read_len < 16 || m.max_len > kAlnWideRead || m.n_local() == 0 || m.bucket_hash.empty());
 }
+
+// which instantiation this mate's own launches take
+inline bool aln_wide(const ShortMate& m) { return m.max_len > kAlnMaxRead; }
 
 // window strings (graph.cc:846-857) of the pending windows, concatenated
 void aln_prepare(const gaml_hip_ctx* c, const ShortMate& m, AlnJob& job) {
@@ -135,12 +147,12 @@ int aln_small_enqueue(gaml_hip_ctx* c, const ShortMate& m, AlignDev& d, AlignSma
   const AlnWindow* d_wins = (const AlnWindow*)dbase;
   const int* d_blk = (const int*)(dbase + off_blk);
   const char* d_wstr = dbase + off_str;
-  hipLaunchKernelGGL(span_maxima_kernel, dim3((unsigned)job.blk[(size_t)nw]), dim3(kAlnBlock), 0, st, d_wstr, d_wins, nw, m.index_read_len, d_blk,
+  ALN_LAUNCH(aln_wide(m), span_maxima_kernel, dim3((unsigned)job.blk[(size_t)nw]), dim3(kAlnBlock), 0, st, d_wstr, d_wins, nw, m.index_read_len, d_blk,
                      S.spans.as<AlnSpan>(), S.counters.as<unsigned>(), kFastSpans);
   hipLaunchKernelGGL(candidates_kernel, dim3(64), dim3(kAlnBlock), 0, st, S.spans.as<AlnSpan>(), S.counters.as<unsigned>(), kFastSpans,
                      d.bucket_hash.as<uint64_t>(), d.bucket_top.as<int32_t>(), d.bucket_off.as<int32_t>(), d.bucket_reads.as<int32_t>(), (int)m.bucket_hash.size(), S.cands.as<AlnCand>(),
                      S.counters.as<unsigned>() + 1, kFastCands);
-  hipLaunchKernelGGL(extend_kernel, dim3(1024), dim3(64 * kAlnWaves), 0, st, S.cands.as<AlnCand>(), S.counters.as<unsigned>() + 1, kFastCands, d_wstr,
+  ALN_LAUNCH(aln_wide(m), extend_kernel, dim3(1024), dim3(64 * kAlnWaves), 0, st, S.cands.as<AlnCand>(), S.counters.as<unsigned>() + 1, kFastCands, d_wstr,
                      d_wins, d.reads.as<char>(), d.read_off.as<int64_t>(), S.hits.as<AlnHit>());
   job.seq = ++S.out_seq;
   char* oh = (char*)S.out_host.dev;
@@ -384,6 +396,7 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
     ix.reads[mt] = d.reads.as<char>(); ix.read_off[mt] = d.read_off.as<int64_t>();
   }
   ix.split = n0;
+  const bool wide = aln_wide(*mm[0]) || aln_wide(*mm[1]);  // one kernel serves both mates
   // two dispatches: spans + candidates, then the extension, whose last block publishes (aligner_small.hip.h)
 #ifdef GAML_ALN_STAMPS
   {
@@ -402,11 +415,11 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
   }
 #ifdef GAML_ALN_STAMPS
   if (getenv("GAML_ALN_TWICE")) {  // the same batch once before, unstamped results thrown away: does a warm instruction cache change the stamps?
-    hipLaunchKernelGGL(span_cands_kernel, dim3((unsigned)job.blk[(size_t)nw]), dim3(kAlnBlock), 0, st, sa, in_args ? 1 : 0, d_wstr, d_wins, nw, mm[0]->index_read_len, d_blk, n0,
+    ALN_LAUNCH(wide, span_cands_kernel, dim3((unsigned)job.blk[(size_t)nw]), dim3(kAlnBlock), 0, st, sa, in_args ? 1 : 0, d_wstr, d_wins, nw, mm[0]->index_read_len, d_blk, n0,
                        mm[1]->index_read_len, ix, wa, S.cands.as<AlnCandX>(), S.counters.as<unsigned>() + 1, kFastCands, S.wcopy.as<char>());
     const unsigned long long sq = ++S.out_seq;
     char* oh0 = (char*)S.out_host.dev;
-    hipLaunchKernelGGL(extend_pair2_kernel, dim3(512), dim3(128 * kAlnPairs), 0, st, sa, in_args ? 1 : 0, S.cands.as<AlnCandX>(), S.counters.as<unsigned>(), kFastCands, S.wcopy.as<char>(), ix,
+    ALN_LAUNCH(wide, extend_pair2_kernel, dim3(512), dim3(128 * kAlnPairs), 0, st, sa, in_args ? 1 : 0, S.cands.as<AlnCandX>(), S.counters.as<unsigned>(), kFastCands, S.wcopy.as<char>(), ix,
                        (AlnHit*)(oh0 + 128), (unsigned*)(oh0 + 64), (volatile unsigned long long*)oh0, sq, S.hits.as<AlnHit>());
     unsigned long long z[32];
     for (int k = 0; k < 32; k++) z[k] = (k == 0 || k == 8) ? ~0ull : 0ull;
@@ -425,7 +438,7 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
   hipEvent_t aev[4] = {nullptr, nullptr, nullptr, nullptr};
 #endif
   const double ta = now_us();
-  hipExtLaunchKernelGGL(span_cands_kernel, dim3((unsigned)job.blk[(size_t)nw]), dim3(kAlnBlock), 0, st, timed ? aev[0] : nullptr, timed ? aev[1] : nullptr, 0, sa, in_args ? 1 : 0, d_wstr, d_wins, nw, mm[0]->index_read_len, d_blk, n0,
+  ALN_EXT_LAUNCH(wide, span_cands_kernel, dim3((unsigned)job.blk[(size_t)nw]), dim3(kAlnBlock), 0, st, timed ? aev[0] : nullptr, timed ? aev[1] : nullptr, 0, sa, in_args ? 1 : 0, d_wstr, d_wins, nw, mm[0]->index_read_len, d_blk, n0,
                         mm[1]->index_read_len, ix, wa, S.cands.as<AlnCandX>(), S.counters.as<unsigned>() + 1, kFastCands, S.wcopy.as<char>(),
                         timed ? (unsigned long long*)((char*)S.out_host.dev + 32) : nullptr, S.out_seq + 1);
   double tb = now_us();
@@ -446,7 +459,7 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
     for (int mt = 0; mt < 2; mt++) if (int e = pool_reserve(c, ps, mt, ps.dev[mt].pool_n + kFileMaxHits)) return e;
     if (int e = pool_mirror(c, ps, st)) return e;  // (windows the host filed earlier come first in the pools)
   }
-  hipExtLaunchKernelGGL(extend_pair2_kernel, dim3(512), dim3(128 * kAlnPairs), 0, st, timed ? aev[2] : nullptr, timed ? aev[3] : nullptr, 0, sa, in_args ? 1 : 0, S.cands.as<AlnCandX>(), S.counters.as<unsigned>(), kFastCands, S.wcopy.as<char>(), ix,
+  ALN_EXT_LAUNCH(wide, extend_pair2_kernel, dim3(512), dim3(128 * kAlnPairs), 0, st, timed ? aev[2] : nullptr, timed ? aev[3] : nullptr, 0, sa, in_args ? 1 : 0, S.cands.as<AlnCandX>(), S.counters.as<unsigned>(), kFastCands, S.wcopy.as<char>(), ix,
                         (AlnHit*)(oh + 128), (unsigned*)(oh + 64), (volatile unsigned long long*)oh, job.seq, S.hits.as<AlnHit>(), file_dev ? 1 : 0);
   if (file_dev) {
     AlnFileArgs fa;
@@ -610,7 +623,7 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
     HIP_TRY(c, S.cands.reserve(cap_cands * sizeof(AlnCand)));
     HIP_TRY(c, hipMemsetAsync(S.counters.p, 0, 16, st));
     if (blk[(size_t)nw] > 0) {
-      hipLaunchKernelGGL(span_maxima_kernel, dim3((unsigned)blk[(size_t)nw]), dim3(kAlnBlock), 0, st, S.wstr.as<char>(), S.wins.as<AlnWindow>(), nw,
+      ALN_LAUNCH(aln_wide(m), span_maxima_kernel, dim3((unsigned)blk[(size_t)nw]), dim3(kAlnBlock), 0, st, S.wstr.as<char>(), S.wins.as<AlnWindow>(), nw,
                          m.index_read_len, S.blk.as<int>(), S.spans.as<AlnSpan>(), S.counters.as<unsigned>(), (unsigned)cap_spans);
       HIP_TRY(c, hipGetLastError());
     }
@@ -630,7 +643,7 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
   nc = counts[1];
   if (nc) {
     HIP_TRY(c, S.hits.reserve((size_t)nc * sizeof(AlnHit)));
-    hipLaunchKernelGGL(extend_kernel, dim3((nc + kAlnWaves - 1) / kAlnWaves), dim3(64 * kAlnWaves), 0, st, S.cands.as<AlnCand>(), S.counters.as<unsigned>() + 1,
+    ALN_LAUNCH(aln_wide(m), extend_kernel, dim3((nc + kAlnWaves - 1) / kAlnWaves), dim3(64 * kAlnWaves), 0, st, S.cands.as<AlnCand>(), S.counters.as<unsigned>() + 1,
                        (unsigned)cap_cands, S.wstr.as<char>(), S.wins.as<AlnWindow>(), d.reads.as<char>(), d.read_off.as<int64_t>(),
                        S.hits.as<AlnHit>());
     HIP_TRY(c, hipGetLastError());

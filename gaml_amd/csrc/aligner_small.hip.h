@@ -15,6 +15,8 @@
 //                       of LDS -- was tried: bit-equal and three to four times SLOWER per chain head.)
 //                       Hits go straight to mapped pinned host memory; the block that finishes last publishes the
 //                       counts and the sequence word the host polls, and leaves the counters at zero.
+// Both kernels take the longest read as a template parameter (AlnLim, aligner.hip.h); a batch runs both mates in one
+// kernel, so it takes the wide instantiation when either mate has a read above 254 bases.
 #pragma once
 #include "aligner.hip.h"
 
@@ -65,10 +67,11 @@ __device__ __forceinline__ const char* aln_arg_strings(const char* fallback, int
 #endif
 }
 // (windows [split, n_win) belong to a second read set -- the other mate -- whose index was built for read length R2)
+template <int MR>
 __global__ __launch_bounds__(kAlnBlock) void span_cands_kernel(AlnStrArgs, int str_in_args, const char* wstr, const AlnWindow* wins, int n_win, int R, const int* blk, int split, int R2,
                                                               AlnMates ix, AlnWinArgs wa, AlnCandX* cands, unsigned* n_cands, unsigned cap_cands, char* wcopy,
                                                               unsigned long long* h_started = nullptr, unsigned long long started_seq = 0) {
-  __shared__ AlnSpanLds L;
+  __shared__ AlnSpanLds<MR> L;
   __shared__ int sh_pref[kAlnBlock], sh_b0[kAlnBlock], sh_p[kAlnBlock];
   __shared__ int sh_wave[kAlnBlock / 64];
   __shared__ unsigned sh_base;
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(kAlnBlock) void span_cands_kernel(AlnStrArgs, int s
   }
   wstr = aln_arg_strings(wstr, str_in_args);
   const int w = wa.n > 0 ? aln_span_locate(wa.blk, wa.w, wa.n, win, rel) : aln_span_locate(blk, wins, n_win, win, rel);
-  if (!aln_span_front(L, wstr, win, w, rel, w >= split ? R2 : R, o, wcopy)) return;
+  if (!aln_span_front<MR>(L, wstr, win, w, rel, w >= split ? R2 : R, o, wcopy)) return;
   ALN_STAMP(2);
   const int mt = o.w >= ix.split ? 1 : 0;  // block-uniform, like o.w and o.strand
   int b0 = 0, cnt = 0;
@@ -137,14 +140,17 @@ __global__ __launch_bounds__(kAlnBlock) void span_cands_kernel(AlnStrArgs, int s
   ALN_STAMP(5);
 }
 
-using AlnWave2Lds = AlnWaveLdsT<2 * kAlnMaxRead + 16>;  // ws: the window bases ANY placement of the seed in the read can reach
+template <int MR>
+using AlnWave2Lds = AlnWaveLdsT<MR, 2 * MR + 16>;        // ws: the window bases ANY placement of the seed in the read can reach
 constexpr int kAlnPairs = 2;                             // candidates per block (two waves each)
 constexpr int kAlnTicketWord = 32;                       // counters[32]: working blocks done -- a cache line of its own
 
 // counters: [1] candidates (span_cands_kernel), [kAlnTicketWord] working blocks done. h_counts / h_hits / h_seq: mapped pinned host memory.
+template <int MR>
 __global__ __launch_bounds__(128 * kAlnPairs) void extend_pair2_kernel(AlnStrArgs, int str_in_args, const AlnCandX* cands, unsigned* counters, unsigned cap_cands, const char* wstr, AlnMates ix,
                                                                       AlnHit* h_hits, unsigned* h_counts, volatile unsigned long long* h_seq, unsigned long long seq, AlnHit* d_hits, int file_on_device = 0) {
-  __shared__ AlnWave2Lds lds_all[2 * kAlnPairs];
+  __shared__ AlnWave2Lds<MR> lds_all[2 * kAlnPairs];
+  constexpr int kRdRounds = AlnLim<MR>::kReadRounds, kWsRounds = AlnLim<MR>::kSegRounds;  // 64 bytes per lane round: R <= 64 kRdRounds, seg_end - seg0 <= 2 R - 3 <= 64 kWsRounds
   __shared__ int sh_res[kAlnPairs][4];
   __shared__ int sh_last;
   ALN_STAMP_FIRST(8); ALN_STAMP(9);
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(128 * kAlnPairs) void extend_pair2_kernel(AlnStrArg
   const unsigned n_cands = counters[1];
   const unsigned n = n_cands <= cap_cands ? n_cands : 0u;  // overflow: counts only, the host takes the other route
   const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6), pair = wv >> 1, dir = wv & 1;
-  AlnWave2Lds& L = lds_all[wv];
+  AlnWave2Lds<MR>& L = lds_all[wv];
   for (unsigned base = blockIdx.x * kAlnPairs; base < n; base += gridDim.x * kAlnPairs) {  // (block-uniform trip count: the barriers below)
     const unsigned t = base + (unsigned)pair;
     const bool live = t < n;
@@ -168,7 +174,7 @@ __global__ __launch_bounds__(128 * kAlnPairs) void extend_pair2_kernel(AlnStrArg
 #endif
       ALN_STAMP(10);
       const int R = c.rlen, W = c.w_len;
-      if (R <= kAlnMaxRead && R >= kAlnSeed) {
+      if (R <= MR && R >= kAlnSeed) {
         const char* ws = wstr + c.w_off;  // ProcessHit always works on the FORWARD window string
         const char* rd = (__builtin_amdgcn_readfirstlane(c.mate) ? ix.reads[1] : ix.reads[0]) + c.roff;  // (a select between kernel arguments: indexing them by a loaded value is a VECTOR load from the argument segment, 10 us on first touch)
         // seed start in the forward window string (graph.cc:866-872)
@@ -177,29 +183,29 @@ __global__ __launch_bounds__(128 * kAlnPairs) void extend_pair2_kernel(AlnStrArg
         const int seg0 = max(0, win_pos - (R - kAlnSeed) - 6), seg_end = min(W, win_pos + R + 6);
         // the read as aligned: strand 1 = reverse complement of the stored read (graph.cc:873-876). Every byte is requested
         // before the first one is used: a load per loop iteration, each waiting for the previous LDS store, was 10 us.
-        unsigned char rb[4], wb[8];
+        unsigned char rb[kRdRounds], wb[kWsRounds];
 #ifdef GAML_ALN_STAMPS
         { unsigned long long pv = (unsigned long long)rd; asm volatile("s_waitcnt vmcnt(0)" : "+v"(pv) :: "memory"); ALN_STAMP(18); }
 #endif
 #pragma unroll
-        for (int u = 0; u < 4; u++) { const int b = lane + 64 * u; rb[u] = b < R ? (unsigned char)rd[b] : (unsigned char)0; }
+        for (int u = 0; u < kRdRounds; u++) { const int b = lane + 64 * u; rb[u] = b < R ? (unsigned char)rd[b] : (unsigned char)0; }
 #ifdef GAML_ALN_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ALN_STAMP(19);
 #endif
 #pragma unroll
-        for (int u = 0; u < 8; u++) { const int b = lane + 64 * u; wb[u] = b < seg_end - seg0 ? (unsigned char)ws[seg0 + b] : (unsigned char)0; }
+        for (int u = 0; u < kWsRounds; u++) { const int b = lane + 64 * u; wb[u] = b < seg_end - seg0 ? (unsigned char)ws[seg0 + b] : (unsigned char)0; }
 #ifdef GAML_ALN_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ALN_STAMP(17);
 #endif
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
+        for (int u = 0; u < kRdRounds; u++) {
           const int b = lane + 64 * u;
           if (b < R) { if (c.strand == 0) L.rd[b] = rb[u]; else L.rd[R - 1 - b] = (unsigned char)aln_comp((char)rb[u]); }
         }
 #pragma unroll
-        for (int u = 0; u < 8; u++) { const int b = lane + 64 * u; if (b < seg_end - seg0) L.ws[b] = wb[u]; }
+        for (int u = 0; u < kWsRounds; u++) { const int b = lane + 64 * u; if (b < seg_end - seg0) L.ws[b] = wb[u]; }
         aln_lds_sync();
         ALN_STAMP(11);
         // first position of the (oriented) read carrying the window's seed (graph.cc:873-879): 64 positions at a time
@@ -208,17 +214,17 @@ __global__ __launch_bounds__(128 * kAlnPairs) void extend_pair2_kernel(AlnStrArg
           const int i = b0 + lane;
           bool same = i + kAlnSeed <= R;
 #pragma unroll
-          for (int k = 0; k < kAlnSeed; k++) same = same & (L.rd[min(i + k, kAlnMaxRead)] == L.ws[win_pos - seg0 + k]);
+          for (int k = 0; k < kAlnSeed; k++) same = same & (L.rd[min(i + k, MR)] == L.ws[win_pos - seg0 + k]);
           const unsigned long long hit = __ballot(same);
           if (hit) read_pos = b0 + (__ffsll((long long)hit) - 1);
         }
         ALN_STAMP(12);
         if (read_pos >= 0) {
           auto wbase = [&](int g) -> unsigned char {  // the reference reads the terminator at g == W
-            const unsigned char v = L.ws[min(max(g - seg0, 0), 2 * kAlnMaxRead + 15)];
+            const unsigned char v = L.ws[min(max(g - seg0, 0), 2 * MR + 15)];
             return (g >= seg0 && g < seg_end) ? v : (unsigned char)'\0';
           };
-          AlnWaveSearch<AlnWave2Lds> S(L, lane);
+          AlnWaveSearch<AlnWave2Lds<MR>> S(L, lane);
           res = dir == 0 ? S.forward(wbase, R, W, win_pos, read_pos) : S.backward(wbase, W, win_pos, read_pos, begin_pos);
         }
       }

@@ -435,6 +435,8 @@ WORKLOADS = {
     "cfg2": Workload("cfg2: 1 Mbp, 30x 2x150 paired, insert 300+-30", 1_000_000, 100_000),
     "cfg3": Workload("cfg3: 5 Mbp, 50x 2x150 paired, insert 300+-30", 5_000_000, 833_333),
     "tiny": Workload("tiny: 60 kbp, 2x150 paired", 60_000, 3_000),
+    # cfg2's shape with a MiSeq 2x300 library: reads above 254 bases take the aligner's wide kernels (aligner.hip.h)
+    "cfg2x300": Workload("cfg2x300: 1 Mbp, 2x300 paired, insert 660+-66", 1_000_000, 100_000, read_len=300, insert_mean=660.0, insert_std=66.0),
     # "optionally with planted repeats" -- config 3's recipe with 2 % of the genome in collapsed 5-copy repeat
     # families of 1-3 kbp: the true walk visits those nodes five times (windows that occur several times: general path)
     "cfg3r": Workload("cfg3r: 5 Mbp + 2 % collapsed 5-copy repeats of 1-3 kbp, 50x 2x150 paired, insert 300+-30", 5_000_000, 850_000, repeat_frac=0.02),

@@ -375,6 +375,9 @@ int64_t gaml_hip_window_records(gaml_hip_ctx* ctx, int readset, int mate, const 
 /* force alignment of one window with the library's own aligner (AlignSubpathInternal graph.cc:839-899) */
 int64_t gaml_hip_align_window(gaml_hip_ctx* ctx, int readset, int mate, const int32_t* subpath, int32_t subpath_len);
 /* GPU window aligner (cold path): windows aligned on the device so far, seed candidates extended, wall time.
+ * The device aligns the windows of a paired set's mate whose reads have at most 510 bases and whose indexed read
+ * length is at least 16; every other mate, single-end sets and host-only contexts are served by the library's host
+ * aligner with identical records, and do not count here -- counters that stay at zero mean the host aligner ran.
  * (Development builds: knob 5 = 1, gaml_hip_debug.h, forces the host aligner.) */
 int gaml_hip_aligner_stats(gaml_hip_ctx* ctx, int64_t* windows, int64_t* candidates, double* microseconds);
 /* the same time by stage, host clock, cumulative: out6 = {window strings + upload, spans + candidates (small batches: the
