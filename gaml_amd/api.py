@@ -195,6 +195,9 @@ def _load():
         L.gaml_hip_debug_table_occurrences.argtypes = [vp, C.c_int, C.c_int, _i32p, C.c_int64, _i64p]
     if hasattr(L, "gaml_hip_debug_table_occurrences"):  # development build only
         L.gaml_hip_debug_table_occurrences.restype = C.c_int64
+    if hasattr(L, "gaml_hip_debug_cov_layout"):  # development build only
+        L.gaml_hip_debug_cov_layout.argtypes = [vp, C.c_int, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, vp]
+        L.gaml_hip_debug_cov_layout.restype = C.c_int32
     if hasattr(L, "gaml_hip_debug_window_walk"):  # development build only
         L.gaml_hip_debug_window_walk.argtypes = [vp, C.c_int, C.c_int, C.c_int32, _i32p, C.c_int32]
     for new, old in (("gaml_hip_pair_classes", "gaml_hip_debug_class_counts"), ("gaml_hip_last_phases", "gaml_hip_debug_profile"),
@@ -756,6 +759,19 @@ class Context:
         out = np.zeros(5 * max(1, n), np.int32)
         _lib.gaml_hip_debug_table_occurrences(self._h, rs, mate, out, n, info)
         return out.reshape(-1, 5)[:n], {"incremental": bool(info[0]), "incremental_calls": int(info[1]), "full_calls": int(info[2])}
+
+    def debug_cov_layout(self, rs):
+        """The coverage bitmap layout of the last prepare / evaluation of a penalised paired set: {slot_base [slots],
+        path_base [paths + 1], start_off [paths + 1], starts, slots [paths], total_bits} (gaml_hip_debug_cov_layout)."""
+        cnt = np.zeros(4, np.int32)
+        z = np.zeros(2, np.int32)
+        n = _lib.gaml_hip_debug_cov_layout(self._h, rs, z.ctypes.data, 0, z.ctypes.data, z.ctypes.data, z.ctypes.data, 0, z.ctypes.data, 0, cnt.ctypes.data)
+        if n < 0:
+            raise GamlHipError(n, "no coverage layout: the set has no penalty or nothing was prepared")
+        sb, pb, so = np.zeros(max(1, cnt[0]), np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+        sl, st = np.zeros(max(1, n), np.int32), np.zeros(max(1, cnt[2]), np.int32)
+        _lib.gaml_hip_debug_cov_layout(self._h, rs, sb.ctypes.data, len(sb), pb.ctypes.data, so.ctypes.data, sl.ctypes.data, max(1, n), st.ctypes.data, len(st), cnt.ctypes.data)
+        return {"slot_base": sb[:cnt[0]], "path_base": pb, "start_off": so, "starts": st[:cnt[2]], "slots": sl[:n], "total_bits": int(cnt[3])}
 
     def debug_window_walk(self, rs, mate, wid) -> list:
         buf = np.zeros(64, np.int32)

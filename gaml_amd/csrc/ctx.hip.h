@@ -325,7 +325,9 @@ struct PairedSet {
     void* dev = nullptr; size_t bytes = 0;
     size_t cap_w[2] = {0, 0}, cap_lo[2] = {0, 0}, cap_m[2] = {0, 0};  // table entries / list bounds / list entries per mate
     size_t off_tfloor = 0, off_occ[2] = {0, 0}, off_lo[2] = {0, 0}, off_m[2] = {0, 0};
+    size_t cap_cov = 0, off_cov = 0;   // coverage layout of the call (penalty_constant > 0): int32 entries / where they start; written whole per call
     bool valid = false;                // the copy mirrors the host images as of their last take_changed()
+    size_t last_bytes = 0;             // table entries + coverage layout the last update wrote (gaml_hip_last_phases()[6])
     void release() { if (dev) (void)hipFree(dev); dev = nullptr; bytes = 0; valid = false; }
   } persist;
   // Whole-set blocking calls on the resident route build the occurrence tables on the device (occ_device.hip.h): every
@@ -437,7 +439,10 @@ struct PacbioSet {
 
 struct PairedPrep {
   int64_t assembled_records = 0;  // records the reference would touch in GetPositionsOnlyPath
-  std::vector<int32_t> path_base, start_off, starts;
+  // coverage bitmap layout (penalty_constant > 0). The scoring kernels mark through slot_base[path slot of the table entry];
+  // the sweep walks the paths in set order: path_base[k] (monotone: it finds a word's path by binary search), the contig
+  // starts of path k at starts[start_off[k] .. start_off[k + 1]). slot_base[slots[k]] == path_base[k].
+  std::vector<int32_t> slot_base, path_base, start_off, starts;
   int32_t total_bits = 0, n_paths = 0;
   bool general = false;           // some window occurs several times in this path set: the GEN instantiation of the scoring kernels
 };

@@ -62,6 +62,28 @@ int64_t gaml_hip_debug_table_occurrences(gaml_hip_ctx* c, int rs, int mate, int3
   return (int64_t)v.size();
 }
 
+int32_t gaml_hip_debug_cov_layout(gaml_hip_ctx* c, int rs, int32_t* slot_base, int32_t cap_slots, int32_t* path_base, int32_t* start_off, int32_t* slots,
+                                   int32_t cap_paths, int32_t* starts, int32_t cap_starts, int32_t* counts4) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1) return -1;
+  PairedSet& ps = *c->paireds[c->handles[rs].idx];
+  if (!(ps.cfg.penalty_constant > 0) || ps.planner.full_calls + ps.planner.incremental_calls == 0) return -1;  // no penalty, or nothing prepared yet
+  struct { std::vector<int32_t> slot_base, path_base, start_off, starts, slots; } L;
+  {
+    PairedPrep p;  // what pass 2 builds for the planner's current set (prepare_paired_tables_host)
+    paired_cov_build(ps, true, p);
+    L.slot_base.swap(p.slot_base); L.path_base.swap(p.path_base); L.start_off.swap(p.start_off); L.starts.swap(p.starts);
+    L.slots = ps.planner.slots();
+  }
+  const int32_t n = (int32_t)L.slots.size();
+  if (counts4) { counts4[0] = (int32_t)L.slot_base.size(); counts4[1] = n; counts4[2] = (int32_t)L.starts.size(); counts4[3] = L.path_base.back(); }
+  for (int32_t k = 0; k < (int32_t)L.slot_base.size() && k < cap_slots; k++) slot_base[k] = L.slot_base[k];
+  for (int32_t k = 0; k <= n && k <= cap_paths && cap_paths > 0; k++) { path_base[k] = L.path_base[k]; start_off[k] = L.start_off[k]; }
+  for (int32_t k = 0; k < n && k < cap_paths; k++) slots[k] = L.slots[k];
+  for (int32_t k = 0; k < (int32_t)L.starts.size() && k < cap_starts; k++) starts[k] = L.starts[k];
+  return n;
+}
+
 int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* c, int rs, int mate, int32_t wid, int32_t* out, int32_t cap) {
   MULTI_SHARD0(c);
   ShortMate* m = mate_of(c, rs, mate);

@@ -159,7 +159,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     r.L.tfloor_off = P.off_tfloor;
     r.L.l0 = OccLayout{P.off_occ[0], P.off_lo[0], P.off_m[0], P.off_lo[1] /* unused */};
     r.L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.bytes};
-    r.L.pb_off = r.L.so_off = r.L.st_off = 0; r.L.total = P.bytes;
+    r.L.sb_off = r.L.pb_off = r.L.so_off = r.L.st_off = 0; r.L.total = P.bytes;
     r.Ls.assign((size_t)chunk, r.L);
     { const PairedPrep one = r.prep[0]; r.prep.assign((size_t)chunk, one); }  // every length: the same windows, lists and records
     if (int e = arena_acquire(c, ps.arena, r.stride * (size_t)chunk + r.chg_bytes[0] + r.chg_bytes[1], st, &r.slot, &r.wp)) return e;

@@ -287,7 +287,7 @@ struct OccImage {
   std::vector<int32_t> multi_off;
   std::vector<OccQuad> multi;
   std::vector<int32_t> general_wids;  // windows whose entry sends their reads to the general path
-  // whole path set at once (every path changed, first call, coverage penalty): O(occurrences)
+  // whole path set at once (every path changed, first call): O(occurrences)
   // slots: the path slot of every path of the set (null: slots are positions), pos_of_slot its inverse
   void build(size_t n_windows, const PlanView& view, int mate, const std::vector<int32_t>* slots = nullptr,
              const std::vector<int32_t>* pos_of_slot = nullptr);
@@ -367,7 +367,7 @@ class PairedPlanner {
   // and / or suffix of paths with the previous call's (what an annealing move leaves: it edits one or two paths), only
   // the paths in between are looked at: hashing, registration replay, placements, occurrence lists and the table
   // entries that follow from them are O(changed paths). Returns false (and sets *err) on a node id outside the graph.
-  // allow_incremental = false: everything from scratch (first call, coverage penalty, after the window maxima changed).
+  // allow_incremental = false: everything from scratch (first call, knob 12, after the window maxima changed).
   bool begin(const GraphStore& g, ShortMate mate[2], const int32_t* flat, const int64_t* offs, int32_t n_paths,
              bool allow_incremental, std::string* err);
   void finish(ShortMate mate[2]);          // pass 2 (needs the windows' records / global maxima): occurrence lists
@@ -394,6 +394,7 @@ class PairedPlanner {
   int32_t n_paths() const { return (int32_t)cur_ids_.size(); }
   bool last_was_incremental() const { return incremental_; }
   const std::vector<int32_t>& slots() const { return cur_slots_; }  // slot of every path of the current set
+  int32_t slot_count() const { return next_slot_; }                 // slots handed out so far (every slot in use is below)
   uint64_t hits = 0, misses = 0, incremental_calls = 0, full_calls = 0;
  private:
   int32_t lookup_or_create(const GraphStore& g, const int32_t* p, int32_t len, std::string* err);

@@ -62,7 +62,8 @@ struct PairedArgs {
   const double* covthr_tab;  // exp(c + k*2*L2) indexed by L2 (graph.cc:1855-1857 quirk), or null
   double two_T;              // 2 * total_len as double (graph.cc:1505)
   int n;                     // pairs in this shard
-  const int* path_base;      // bit offset of each path in cov_bits
+  const int* path_base;      // [path slot] bit offset of the path's region in cov_bits (the `path` of an occurrence entry is its slot)
+  double covthr0;            // covthr_c[0] by value (sets with one length combination)
   // class 0 (compact): slots [0, n0): 8-byte records, 1-byte length code, 8-byte occurrence entries
   const unsigned char* len_code;
   const uint32_t* len_combo;
@@ -707,6 +708,16 @@ __device__ __forceinline__ void paired_compact_body(const PairedArgs& a, const S
 // Pairs and their order per lane are those of paired_compact_body (slot = base + k * stride), so both give the
 // same sums bit for bit.
 constexpr int kPairZero = -1, kPairOther = -(1 << 20);
+// The coverage events of a scoring class-0 pair (use_all_to_cov, graph.cc:1883-1888) from the 32-bit halves of its records
+// and occurrence entries: both ends of the pair in the region of its path, slot_base[path slot] + shift + position in the
+// window -- the bits compact_cover sets for the same pair. The caller has compared the pair's term with the threshold.
+__device__ __forceinline__ void cover_marks(const PairedArgs& a, uint2 r1, uint2 r2, uint2 o1, uint2 o2) {
+  const int p1 = (int)(__funnelshift_r(r1.x, r1.y, 24) & 0xfffffffu), p2 = (int)(__funnelshift_r(r2.x, r2.y, 24) & 0xfffffffu);
+  const int x = p1 + (int)o1.x, y = p2 + (int)o2.x;
+  const int base = a.path_base[(o1.y >> 16) & 0x7fffu];
+  mark_bit(a.cov_bits, base + max(x, y));
+  mark_bit(a.cov_bits, base + min(x, y));
+}
 // compact_prep without branches, on the 32-bit halves of the 8-byte record / occurrence words (the scoring kernel
 // is issue-bound at cfg3: the branchy 64-bit form was 156 instructions per pair, a third of a wave's lifetime)
 __device__ __forceinline__ int compact_state(const PairedArgs& a, uint2 r1, uint2 r2, uint2 o1, uint2 o2, unsigned lc, uint32_t l12,
@@ -734,7 +745,9 @@ __device__ __forceinline__ int compact_state(const PairedArgs& a, uint2 r1, uint
 
 // ONE: every pair has the same length combination (n_codes == 1, the usual case): no length-code loads, no LDS tables --
 // the combination and its log-floor are two uniform values.
-template <bool GEN, bool TL = false, bool ONE = false>
+// COV: the set has a coverage penalty -- a pair whose term clears the threshold marks both its ends (cover_marks); pairs
+// settled from the tables again or on the general path mark there (compact_cover, pair_term), as they always did.
+template <bool GEN, bool TL = false, bool ONE = false, bool COV = false>
 __device__ __forceinline__ void paired_compact4_body(const PairedArgs& a, const SlotRange rg, double& lsum, int& zeros) {
   const unsigned stride = (unsigned)rg.blocks * kBlock, n0 = (unsigned)rg.hi;  // (n0: end of this part's slots)
   unsigned long long* tl = TL ? a.timeline + ((size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 8 : nullptr;
@@ -748,6 +761,7 @@ __device__ __forceinline__ void paired_compact4_body(const PairedArgs& a, const 
   char* const probs = (char*)a.probs;
   const uint32_t l12_one = ONE ? a.len_combo[0] : 0u;
   const double logfloor_one = ONE ? a.logfloor_c[0] : 0.0, tfloor_one = ONE ? a.tfloor_c[0] : 0.0, log2T = a.log_two_T;
+  const double covthr_one = COV && ONE ? a.covthr0 : 0.0;
   for (unsigned base = (unsigned)rg.lo + (unsigned)rg.lb * kBlock + threadIdx.x; base < n0; base += 4 * stride) {
     uint2 r1[4], r2[4], o1[4], o2[4];
     unsigned lc[4];
@@ -777,10 +791,12 @@ __device__ __forceinline__ void paired_compact4_body(const PairedArgs& a, const 
     for (int k = 0; k < 4; k++) m[k] = *(const double2*)(memo + (unsigned)max(state[k], 0) * 16u);
     GAML_STAMP(4, (unsigned)(__double2loint(m[0].x) ^ __double2loint(m[1].x) ^ __double2loint(m[2].x) ^ __double2loint(m[3].x)))
     bool other = false;
+    unsigned mark_bits = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       double* const out = (double*)(probs + (base + k * stride) * 8u);
       if (state[k] >= 0) {  // as compact_finish
+        if (COV) mark_bits |= (unsigned)(m[k].x > (ONE ? covthr_one : a.covthr_c[lc[k]])) << k;
         __builtin_nontemporal_store(m[k].x, out);
         const bool floored = m[k].x < (ONE ? tfloor_one : a.tfloor_c[lc[k]]);  // a memo index was built from this pair's length code
         lsum += floored ? (ONE ? logfloor_one : a.logfloor_c[lc[k]]) : m[k].y - log2T;
@@ -790,6 +806,11 @@ __device__ __forceinline__ void paired_compact4_body(const PairedArgs& a, const 
         zeros++;
         lsum += ONE ? logfloor_one : a.logfloor_c[kPairZero - state[k]];
       } else other |= state[k] == kPairOther && !((skip_bits >> k) & 1u);
+    }
+    if (COV) {  // behind the round's sums and stores
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if ((mark_bits >> k) & 1u) cover_marks(a, r1[k], r2[k], o1[k], o2[k]);
     }
     GAML_STAMP(5, 0u)
     if (__any(other)) {
@@ -871,7 +892,7 @@ __global__ __launch_bounds__(kBlock) void static_values_kernel(const int* static
 // Rounds of P pairs per lane, software-pipelined when a lane takes several: a round's occurrence entries are requested,
 // then the NEXT round's records and values, then the round is finished -- its arithmetic and stores run under the next
 // round's loads.
-template <bool GEN, bool TL = false, bool ONE = false>
+template <bool GEN, bool TL = false, bool ONE = false, bool COV = false>
 __device__ __forceinline__ void paired_static4_body(const PairedArgs& a, const SlotRange rg, double& lsum, int& zeros) {
   constexpr int P = GAML_STATIC_P;
   const unsigned stride = (unsigned)rg.blocks * kBlock, n0 = (unsigned)rg.hi;
@@ -884,6 +905,7 @@ __device__ __forceinline__ void paired_static4_body(const PairedArgs& a, const S
   const char* const occ1 = (const char*)a.occ12[1];
   char* const probs = (char*)a.probs;
   const double logfloor_one = ONE ? a.logfloor0 : 0.0, tfloor_one = ONE ? a.tfloor0 : 0.0, log2T = a.log_two_T;
+  const double covthr_one = COV && ONE ? a.covthr0 : 0.0;
   unsigned base = (unsigned)rg.lo + (unsigned)rg.lb * kBlock + threadIdx.x;
   if (base >= n0) return;
   uint2 r1[P], r2[P];
@@ -926,7 +948,7 @@ __device__ __forceinline__ void paired_static4_body(const PairedArgs& a, const S
     // Everything below is straight-line: bit logic on the 32-bit halves, selects instead of branches, every loaded word
     // used unconditionally (a value that is only used inside a branch gets its LOAD moved into that branch by the
     // compiler -- behind a full wait, a round trip of its own; it did that to the fourth pair's records and values).
-    unsigned skip_bits = 0;
+    unsigned skip_bits = 0, mark_bits = 0;
 #pragma unroll
     for (int k = 0; k < P; k++) {
       const bool none1 = r1[k].y == ~0u, none2 = r2[k].y == ~0u;          // no record (or, mate 1, the dirty mark)
@@ -956,6 +978,13 @@ __device__ __forceinline__ void paired_static4_body(const PairedArgs& a, const S
       lsum += add;                                       // (adding 0.0 changes no bit of a sum of negative logs)
       zeros += (int)floored;
       if (counted && !GAML_TIMING_X(2)) __builtin_nontemporal_store(t, (double*)(probs + (base + k * stride) * 8u));
+      // (the streamed value is the memo entry, the product pair_term forms: the marks are compact_cover's)
+      if (COV) mark_bits |= (unsigned)(scores & (t > (ONE ? covthr_one : a.covthr_c[lc[k]]))) << k;
+    }
+    if (COV) {  // behind the round's sums and stores (their registers are free by now: the marks cost the loop none)
+#pragma unroll
+      for (int k = 0; k < P; k++)
+        if ((mark_bits >> k) & 1u) cover_marks(a, r1[k], r2[k], o1[k], o2[k]);
     }
     if (GEN && !GAML_GEN_OFF(1) && __any(skip_bits != 0)) {  // pairs on a window that occurs several times: here, after the round's other pairs
 #pragma unroll 1
@@ -1290,7 +1319,7 @@ __global__ __launch_bounds__(kBlock) void apply_delta_patch_kernel(const Patch* 
 }
 
 // TL: the in-kernel timeline of tools/kernel_timeline.py (a separate instantiation: the product kernels carry none of it)
-template <bool TICKET, bool GEN, bool TL>
+template <bool TICKET, bool GEN, bool TL, bool COV = false>
 __device__ __forceinline__ void paired_main_body(const PairedArgs& a, int lb, double* sh_s, int* sh_z, int4* gen_lds) {
   // `a`: the argument block as the kernel received it; only its leading words (grid layout, partial slots) are read
   // here -- every class takes a fresh view of its own (GAML_FRESH_ARGS)
@@ -1302,24 +1331,27 @@ __device__ __forceinline__ void paired_main_body(const PairedArgs& a, int lb, do
   } else if (GAML_TIMING_X(16) && lb < a.blocks0a) {  // ... or everything but it
   } else if (lb < a.blocks0) {
     GAML_FRESH_ARGS(c, a)
-    const bool wide = c.memo && !c.cov_bits;  // block-uniform: memo present, no coverage marks to set
+    // block-uniform: memo present, and no coverage marks to set -- or the instantiation that sets them (COV; without it a
+    // penalised set takes paired_compact_body, as do sets without a memo)
+    const bool wide = c.memo && (COV || !c.cov_bits);
     const SlotRange rg = compact_range(c, lb);
     const bool stat = wide && lb < c.blocks0a;  // the part of class 0 whose memo indices came with the tables
     if (!TL && wide && c.n_codes == 1) {  // one length combination: no tables, no barrier
-      if (stat) paired_static4_body<GEN, false, true>(c, rg, lsum, zeros);
-      else paired_compact4_body<GEN, false, true>(c, rg, lsum, zeros);
+      if (stat) paired_static4_body<GEN, false, true, COV>(c, rg, lsum, zeros);
+      else paired_compact4_body<GEN, false, true, COV>(c, rg, lsum, zeros);
     } else {
       // the per-length-combination tables of the compact class (<= 256 entries each) are looked up once or twice
       // per pair, each time behind another load: from LDS they cost an LDS access instead of an L2 round trip
       __shared__ uint32_t sh_combo[256];
-      __shared__ double sh_floor[256], sh_logfloor[256], sh_tfloor[256];
-      for (int k = threadIdx.x; k < c.n_codes; k += kBlock) { sh_combo[k] = c.len_combo[k]; sh_floor[k] = c.floor_c[k]; sh_logfloor[k] = c.logfloor_c[k]; sh_tfloor[k] = c.tfloor_c ? c.tfloor_c[k] : 0.0; }
+      __shared__ double sh_floor[256], sh_logfloor[256], sh_tfloor[256], sh_covthr[COV ? 256 : 1];
+      for (int k = threadIdx.x; k < c.n_codes; k += kBlock) { sh_combo[k] = c.len_combo[k]; sh_floor[k] = c.floor_c[k]; sh_logfloor[k] = c.logfloor_c[k]; sh_tfloor[k] = c.tfloor_c ? c.tfloor_c[k] : 0.0; if (COV) sh_covthr[k] = c.covthr_c[k]; }
       __syncthreads();
       PairedArgs b = c;
       b.len_combo = sh_combo; b.floor_c = sh_floor; b.logfloor_c = sh_logfloor; b.tfloor_c = sh_tfloor;
+      if (COV) b.covthr_c = sh_covthr;
       if (TL && (threadIdx.x & 63) == 0) tl[1] = wall_clock64();
-      if (stat) paired_static4_body<GEN, TL>(b, rg, lsum, zeros);
-      else if (wide) paired_compact4_body<GEN, TL>(b, rg, lsum, zeros);
+      if (stat) paired_static4_body<GEN, TL, false, COV>(b, rg, lsum, zeros);
+      else if (wide) paired_compact4_body<GEN, TL, false, COV>(b, rg, lsum, zeros);
       else paired_compact_body<GEN>(b, rg, lsum, zeros);
     }
   } else {
@@ -1499,7 +1531,9 @@ __device__ __forceinline__ void paired_overflow_body(const PairedArgs& a, int ov
 #ifndef GAML_GEN_WAVES
 #define GAML_GEN_WAVES 4
 #endif
-template <bool TICKET, bool GEN = false, bool TL = false>
+// COV: a set with a coverage penalty whose class 0 takes the memo / streamed-value bodies and marks from there (launch_paired
+// picks it for penalised sets without repeated windows; every other combination runs the instantiations without it).
+template <bool TICKET, bool GEN = false, bool TL = false, bool COV = false>
 __global__ __launch_bounds__(kBlock, GEN ? GAML_GEN_WAVES : 5) void paired_score_kernel(PairedArgs a) {
   __shared__ double sh_s[kBlock / 64];
   __shared__ int sh_z[kBlock / 64];
@@ -1514,24 +1548,24 @@ __global__ __launch_bounds__(kBlock, GEN ? GAML_GEN_WAVES : 5) void paired_score
   // its first record -- although the blocks that score nearly all pairs (static part of the compact class, one length
   // combination) need two dozen of its words. Those blocks read `a` directly (its leading words: PairedArgs); every other
   // class takes a fresh view of the block where its code starts (GAML_FRESH_ARGS).
-  if (!TL && lb < a.blocks0a && a.memo && !a.cov_bits && a.n_codes == 1) {
+  if (!TL && lb < a.blocks0a && a.memo && (COV || !a.cov_bits) && a.n_codes == 1) {
     double lsum = 0.0;
     int zeros = 0;
     if (!GAML_TIMING_X(16))
-    paired_static4_body<GEN, false, true>(a, SlotRange{0, a.n0a, lb, a.blocks0a}, lsum, zeros);
+    paired_static4_body<GEN, false, true, COV>(a, SlotRange{0, a.n0a, lb, a.blocks0a}, lsum, zeros);
     block_reduce(lsum, zeros, sh_s, sh_z);
-    if (TICKET) grid_finish(lsum, zeros, lb, a.total_blocks, a.part_sum, a.part_zero, a.ticket, a.out, 0.0, a.n_reads, sh_s, sh_z, a.status_out, a.status_a, a.status_b);
+    if (TICKET) grid_finish(lsum, zeros, lb, a.total_blocks, a.part_sum, a.part_zero, a.ticket, a.out, COV ? -1.0 : 0.0, a.n_reads, sh_s, sh_z, a.status_out, a.status_a, a.status_b);
     else if (threadIdx.x == 0) { a.part_sum[lb] = lsum; a.part_zero[lb] = zeros; }
     return;
   }
-  if (lb < a.main_blocks) paired_main_body<TICKET, GEN, TL>(a, lb, sh_s, sh_z, &cand[0][0][0]);
+  if (lb < a.main_blocks) paired_main_body<TICKET, GEN, TL, COV>(a, lb, sh_s, sh_z, &cand[0][0][0]);
   else if (GAML_GEN_OFF(16)) { if (threadIdx.x == 0) { a.part_sum[lb] = 0.0; a.part_zero[lb] = 0; } }
   else {
     GAML_FRESH_ARGS(c, a)
     paired_overflow_body<TICKET>(c, lb - c.main_blocks, c.total_blocks - c.main_blocks, sh_s, sh_z, cand);
   }
 #else
-  if (lb < a.main_blocks) paired_main_body<TICKET, GEN, TL>(a, lb, sh_s, sh_z, &cand[0][0][0]);
+  if (lb < a.main_blocks) paired_main_body<TICKET, GEN, TL, COV>(a, lb, sh_s, sh_z, &cand[0][0][0]);
   else paired_overflow_body<TICKET>(a, lb - a.main_blocks, a.total_blocks - a.main_blocks, sh_s, sh_z, cand);
 #endif
 }

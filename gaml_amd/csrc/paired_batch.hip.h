@@ -51,7 +51,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     r.L.tfloor_off = P.off_tfloor;
     r.L.l0 = OccLayout{P.off_occ[0], P.off_lo[0], P.off_m[0], P.off_lo[1] /* unused */};
     r.L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.bytes};
-    r.L.pb_off = r.L.so_off = r.L.st_off = 0; r.L.total = P.bytes;
+    r.L.sb_off = r.L.pb_off = r.L.so_off = r.L.st_off = 0; r.L.total = P.bytes;
     r.Ls.assign((size_t)n, r.L);
     r.prep.resize((size_t)n);
     r.patch_off.assign(2 * (size_t)n + 1, 0);

@@ -74,12 +74,36 @@ int prepare_paired_tables(gaml_hip_ctx* c, PairedSet& s) {
 // pass 1: window registration / alignment of missing windows and the placement of cached windows
 // (memoised per distinct path: PairedPlanner)
 int prepare_paired_structure(gaml_hip_ctx* c, PairedSet& s, const int32_t* flat, const int64_t* offs, int32_t n_paths) {
-  // a coverage penalty needs per-path bitmap layout by position (and the sweep's contig starts): whole-set planning;
-  // knob 12 = 1 forces it for A/B runs and tests
-  const bool incremental = !(s.cfg.penalty_constant > 0) && KNOB(c, 12) == 0;
+  // knob 12 = 1 forces whole-set planning for A/B runs and tests. (A coverage penalty does not: the table entries carry the
+  // path slot, and pass 2 lays the bitmap out by slot for the marks and by position for the sweep.)
+  const bool incremental = KNOB(c, 12) == 0;
   std::string err;
   if (!s.planner.begin(c->g, s.mate, flat, offs, n_paths, incremental, &err)) return fail(c, GAML_HIP_EINVAL, err);
   return 0;
+}
+
+// The coverage bitmap layout of the planner's current set (events of type 1, graph.cc:1826,1833-1835), rebuilt whole per call,
+// O(paths + contigs) ints: the regions follow the paths' order in the set (the sweep's arrays must be monotone), the marks
+// find a path's region through its slot -- which, under incremental planning, is not its position.
+void paired_cov_build(PairedSet& s, bool cov, PairedPrep& p) {
+  p.path_base.assign(1, 0);
+  p.start_off.assign(1, 0);
+  p.starts.clear();
+  p.slot_base.assign(1, 0);
+  if (!cov) return;
+  const PlanView& v = s.planner.view();
+  const std::vector<int32_t>& slots = s.planner.slots();
+  p.path_base.reserve(v.paths.size() + 1);
+  p.start_off.reserve(v.paths.size() + 1);
+  p.slot_base.assign((size_t)std::max(1, s.planner.slot_count()), 0);  // (slots not in use: no region, nothing names them)
+  for (size_t k = 0; k < v.paths.size(); k++) {
+    const PathMemo* pm = v.paths[k];
+    p.starts.insert(p.starts.end(), pm->starts.begin(), pm->starts.end());
+    p.start_off.push_back((int32_t)p.starts.size());
+    int32_t bits = ((pm->length + 64 + 31) / 32) * 32;  // one bit per path position, padded to words (+ slack)
+    p.slot_base[(size_t)slots[k]] = p.path_base.back();
+    p.path_base.push_back(p.path_base.back() + bits);
+  }
 }
 
 // pass 2: position-filter thresholds (need the windows' global largest positions) + occurrence images
@@ -97,20 +121,7 @@ int prepare_paired_tables_host(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, hip
   const double q1 = now_us();
   const bool cov = s.cfg.penalty_constant > 0;
   // coverage bitmap layout + contig starts (events of type 1, graph.cc:1826,1833-1835)
-  p.path_base.assign(1, 0);
-  p.start_off.assign(1, 0);
-  p.starts.clear();
-  if (cov) {  // only the coverage sweep reads these (whole-set planning: slots are positions)
-    const PlanView& v = s.planner.view();
-    p.path_base.reserve(v.paths.size() + 1);
-    p.start_off.reserve(v.paths.size() + 1);
-    for (const PathMemo* pm : v.paths) {
-      p.starts.insert(p.starts.end(), pm->starts.begin(), pm->starts.end());
-      p.start_off.push_back((int32_t)p.starts.size());
-      int32_t bits = ((pm->length + 64 + 31) / 32) * 32;  // one bit per path position, padded to words (+ slack)
-      p.path_base.push_back(p.path_base.back() + bits);
-    }
-  }
+  paired_cov_build(s, cov, p);
   p.total_bits = p.path_base.back();
   p.n_paths = s.planner.n_paths();
   const double q2 = now_us();
@@ -141,7 +152,26 @@ double tfloor_for(double floor, double two_T) {
   return x;
 }
 
-struct PairedLayout { size_t tfloor_off; OccLayout l0, l1; size_t pb_off, so_off, st_off, total; };
+struct PairedLayout { size_t tfloor_off; OccLayout l0, l1; size_t sb_off, pb_off, so_off, st_off, total; };  // (sb / pb / so / st: PairedPrep's coverage layout)
+
+// the coverage layout from byte `at` of a ring slot or of the resident copy: [slot_base | path_base | start_off | starts]
+void paired_cov_layout(const PairedPrep& p, size_t at, PairedLayout& L) {
+  L.sb_off = align16(at);
+  L.pb_off = align16(L.sb_off + p.slot_base.size() * sizeof(int32_t));
+  L.so_off = align16(L.pb_off + p.path_base.size() * sizeof(int32_t));
+  L.st_off = align16(L.so_off + p.start_off.size() * sizeof(int32_t));
+  L.total = align16(L.st_off + p.starts.size() * sizeof(int32_t));
+}
+// write-only (dst may be device memory behind the PCIe BAR)
+void paired_cov_pack(const PairedPrep& p, const PairedLayout& L, char* dst) {
+  memcpy(dst + L.sb_off, p.slot_base.data(), p.slot_base.size() * sizeof(int32_t));
+  memcpy(dst + L.pb_off, p.path_base.data(), p.path_base.size() * sizeof(int32_t));
+  memcpy(dst + L.so_off, p.start_off.data(), p.start_off.size() * sizeof(int32_t));
+  if (!p.starts.empty()) memcpy(dst + L.st_off, p.starts.data(), p.starts.size() * sizeof(int32_t));
+}
+size_t paired_cov_ints(const PairedPrep& p) {  // upper bound of the layout's size in ints (three paddings to 16 bytes)
+  return p.slot_base.size() + p.path_base.size() + p.start_off.size() + p.starts.size() + 16;
+}
 
 // pad_to: table entries per mate (a batch pads every set's tables to the window count the batch may reach)
 PairedLayout paired_layout(const PairedSet& s, const PairedPrep& p, const size_t* pad_to = nullptr) {
@@ -150,12 +180,8 @@ PairedLayout paired_layout(const PairedSet& s, const PairedPrep& p, const size_t
   const size_t hdr = align16(256 * sizeof(double));  // thresholds per length code (the table of codes may grow with a rebuild)
   L.l0 = layout_image(s.image[0], hdr, pad_to ? pad_to[0] : 0);
   L.l1 = layout_image(s.image[1], L.l0.end, pad_to ? pad_to[1] : 0);
-  L.pb_off = L.l1.end; L.so_off = L.st_off = 0; L.total = L.l1.end;
-  if (s.cfg.penalty_constant > 0) {
-    L.so_off = align16(L.pb_off + p.path_base.size() * sizeof(int32_t));
-    L.st_off = align16(L.so_off + p.start_off.size() * sizeof(int32_t));
-    L.total = align16(L.st_off + p.starts.size() * sizeof(int32_t));
-  }
+  L.sb_off = L.pb_off = L.l1.end; L.so_off = L.st_off = 0; L.total = L.l1.end;
+  if (s.cfg.penalty_constant > 0) paired_cov_layout(p, L.l1.end, L);
   return L;
 }
 
@@ -174,11 +200,7 @@ void paired_pack_thresholds(const PairedSet& s, const PairedLayout& L, double tw
 void paired_pack(const PairedSet& s, const PairedPrep& p, const PairedLayout& L, char* dst) {
   pack_image(s.image[0], L.l0, dst);
   pack_image(s.image[1], L.l1, dst);
-  if (s.cfg.penalty_constant > 0) {
-    memcpy(dst + L.pb_off, p.path_base.data(), p.path_base.size() * sizeof(int32_t));
-    memcpy(dst + L.so_off, p.start_off.data(), p.start_off.size() * sizeof(int32_t));
-    memcpy(dst + L.st_off, p.starts.data(), p.starts.size() * sizeof(int32_t));
-  }
+  if (s.cfg.penalty_constant > 0) paired_cov_pack(p, L, dst);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -229,11 +251,14 @@ int arena_release(gaml_hip_ctx* c, Arena& A, int k, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------
 // the resident copy of the tables (blocking calls on a large-BAR device): patched in place through the BAR
 // ---------------------------------------------------------------------------------------------------------
-int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream_t st) {
+// cov_L (penalty_constant > 0): receives where this call's coverage layout sits in the copy (offsets from Persist::dev)
+int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream_t st, const PairedPrep* p = nullptr, PairedLayout* cov_L = nullptr) {
   PairedSet::Persist& P = s.persist;
   OccImage* im = s.image;
   size_t need_w[2], need_lo[2], need_m[2];
   bool relayout = P.dev == nullptr;
+  const size_t need_cov = cov_L ? paired_cov_ints(*p) : 0;
+  if (need_cov > P.cap_cov) relayout = true;
   for (int mt = 0; mt < 2; mt++) {
     need_w[mt] = std::max<size_t>(1, im[mt].occ12.size());
     need_lo[mt] = im[mt].multi_off.size();
@@ -254,6 +279,9 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
       P.off_lo[mt] = at; at = align16(at + P.cap_lo[mt] * sizeof(int32_t));
       P.off_m[mt] = at; at = align16(at + P.cap_m[mt] * sizeof(OccQuad));
     }
+    // (the coverage layout: a few ints per path and contig, written whole per call; room for many times the paths there are)
+    P.cap_cov = need_cov ? std::max<size_t>(4 * need_cov, 16384) : 0;
+    P.off_cov = at; at = align16(at + P.cap_cov * sizeof(int32_t));
     if (at > P.bytes) {
       HIP_TRY(c, hipStreamSynchronize(st));
       if (P.dev) { HIP_TRY(c, hipFree(P.dev)); P.dev = nullptr; }
@@ -265,8 +293,10 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
     full = true;
   }
   char* wp = (char*)P.dev;  // write-only: device memory behind the PCIe BAR
+  P.last_bytes = 0;
   for (int mt = 0; mt < 2; mt++) {
     OccImage& t = im[mt];
+    P.last_bytes += (full ? t.occ12.size() : t.changed.size()) * sizeof(Occ12);
     char* occ = wp + P.off_occ[mt];
     if (full) {
       if (!t.occ12.empty()) memcpy(occ, t.occ12.data(), t.occ12.size() * sizeof(Occ12));
@@ -282,6 +312,11 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
   PairedLayout L;  // only the threshold offset is used here
   L.tfloor_off = P.off_tfloor;
   paired_pack_thresholds(s, L, two_T, wp);
+  if (cov_L) {  // fenced with the thresholds below; never read back
+    paired_cov_layout(*p, P.off_cov, *cov_L);
+    paired_cov_pack(*p, *cov_L, wp);
+    P.last_bytes += cov_L->total - cov_L->sb_off;
+  }
   P.valid = true;
   _mm_sfence();  // drain the write-combining buffers; the launch's doorbell write orders behind them
   return 0;
@@ -353,6 +388,7 @@ void paired_base_args(gaml_hip_ctx* c, PairedSet& s, PairedArgs& a, GridPlan& gp
   a.n_codes = (int)std::min<size_t>(256, s.pt.len_combo.size());
   a.len_combo0 = s.pt.len_combo.empty() ? 0xffffffffu : s.pt.len_combo[0];
   a.logfloor0 = s.pt.len_combo.empty() ? 0.0 : s.logfloor_tab[(s.pt.len_combo[0] & 0xffff) + (s.pt.len_combo[0] >> 16)];  // = logfloor_c[0], by value
+  a.covthr0 = s.pt.len_combo.empty() ? 0.0 : s.covthr_tab[s.pt.len_combo[0] >> 16];  // = covthr_c[0], by value
   a.memo = s.memo_codes > 0 ? s.memo.as<double2>() : nullptr;
   a.lt_codes = s.memo_codes;
   // the delta lists are maintained on the device: the kernels read their exact counts there (PairedArgs::dstate); the host
@@ -488,10 +524,10 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     for (int mt = 0; mt < 2; mt++) sd.occ12[mt] = occdev_table(s, mt);
     c->prof[6] += 256.0 * sizeof(double);
   } else if (resident) {
-    c->prof[6] = (double)((s.image[0].changed_all || s.image[1].changed_all || !s.persist.valid) ? (s.image[0].occ12.size() + s.image[1].occ12.size()) * sizeof(Occ12)
-                                                                                            : (s.image[0].changed.size() + s.image[1].changed.size()) * sizeof(Occ12));
-    if (int e = paired_persist_update(c, s, (double)(2 * tl), st)) return e;
+    if (int e = paired_persist_update(c, s, (double)(2 * tl), st, &p, cov ? &L : nullptr)) return e;
     paired_persist_view(s, total_len, sd);
+    c->prof[6] = (double)s.persist.last_bytes;  // entries written (all of them after a relayout) + the coverage layout
+    if (cov) arena = (const char*)s.persist.dev;  // the call's coverage layout sits in the resident copy too
   } else {
     L = paired_layout(s, p);
     char* wp = nullptr;
@@ -516,7 +552,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     HIP_TRY(c, hipMemsetAsync(s.cov_bits.p, 0, std::max<size_t>(4, words * 4), st));
     HIP_TRY(c, hipMemsetAsync(s.bad.p, 0, sizeof(unsigned long long), st));
     a.cov_bits = s.cov_bits.as<uint32_t>();
-    a.path_base = (const int*)(arena + L.pb_off);
+    a.path_base = (const int*)(arena + L.sb_off);  // by path slot
   }
   // some window occurs several times in this path set (or needs the long occurrence form): the GEN instantiation, whose
   // lanes score such a pair where they meet it
@@ -564,6 +600,8 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     else
 #endif
     if (gen_set) { if (fin_mode) GAML_LAUNCH_SCORE(false, true); else GAML_LAUNCH_SCORE(true, true); }
+    // a penalised set (no repeated windows, memo present): class 0 marks from the memo / streamed-value bodies
+    else if (cov && a.memo && KNOB(c, 21) == 0) { if (fin_mode) GAML_LAUNCH_SCORE(false, false, false, true); else GAML_LAUNCH_SCORE(true, false, false, true); }
     else if (fin_mode) GAML_LAUNCH_SCORE(false, false);
     else GAML_LAUNCH_SCORE(true, false);
 #undef GAML_LAUNCH_SCORE

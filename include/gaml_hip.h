@@ -397,7 +397,8 @@ int gaml_hip_table_stats(gaml_hip_ctx* ctx, int readset, int64_t* out10);
 /* host-side phase times of the last blocking paired evaluation, microseconds: [0] pass 1 (planner; includes [2]),
  * [1] thresholds + occurrence tables, [2] alignment of newly registered windows (inside pass 1), [3] per-call tables
  * written, [4] record tables / delta lists brought up to date, [5] kernel launches, [6] bytes of per-call tables
- * written (a call whose tables the device built: memo entries uploaded + thresholds), [7] wait for the device */
+ * written (a call whose tables the device built: memo entries uploaded + thresholds; a set with a coverage penalty: plus
+ * its coverage bitmap layout, which is written whole per call), [7] wait for the device */
 int gaml_hip_last_phases(gaml_hip_ctx* ctx, double* out8);
 /* timing of the last scoring call, microseconds: [0] host preparation (window registration,
  * alignment of new windows, occurrence tables), [1] H2D + kernels + D2H wall, [2] device time

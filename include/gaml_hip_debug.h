@@ -47,6 +47,15 @@ int64_t gaml_hip_debug_occurrences(gaml_hip_ctx* ctx, int readset, int mate, int
  * the same occurrences as gaml_hip_debug_occurrences. info3 (may be NULL): {1 if the last planning was incremental,
  * incremental calls so far, whole-set calls so far}. */
 int64_t gaml_hip_debug_table_occurrences(gaml_hip_ctx* ctx, int readset, int mate, int32_t* out5, int64_t cap, int64_t* info3);
+/* The coverage bitmap layout of the path set of the last prepare/evaluation of paired set `readset` (penalty_constant > 0): slot_base[slot]
+ * = first bit of the region of the path whose table entries carry that slot (what the scoring kernels mark through; 0 for
+ * slots not in use), and in the order of the paths in the set path_base[n_paths + 1] (monotone, multiples of 32; a path
+ * keeps its length + 64 bits rounded up to words), start_off[n_paths + 1] / starts[] (the contig start coordinates of
+ * path k: starts[start_off[k] .. start_off[k + 1]), what the sweep reads) and slots[n_paths]. counts4 (may be NULL) =
+ * {slots, paths, contig starts, bits in all}; path_base / start_off need room for cap_paths + 1 entries. Returns the
+ * number of paths, -1 when the set has no penalty or nothing was prepared. Works on a host-only context. */
+int32_t gaml_hip_debug_cov_layout(gaml_hip_ctx* ctx, int readset, int32_t* slot_base, int32_t cap_slots, int32_t* path_base, int32_t* start_off,
+                                  int32_t* slots, int32_t cap_paths, int32_t* starts, int32_t cap_starts, int32_t* counts4);
 /* node ids of a cached window (by id); returns its length, -1 if the id is unknown */
 int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int32_t window_id, int32_t* out, int32_t cap);
 /* ---- tuning ------------------------------------------------------------------------------------- */
@@ -66,7 +75,8 @@ int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int
  * same values either way), 18 = d > 1: tables are rebuilt when the delta lists pass pairs / d (default 8), 18 = 1: gap profiles take their
  * fallback route (gaml_hip_gap_profile; the rebuild rule stays the default), 19 = 1: no static
  * memo indices (takes effect at the next table build; same values either way), 20 = blocks of the compact class's second
- * part, 22 = 1: delta maintenance by one-block launches only (default: multi-block
+ * part, 21 = 1: a set with a coverage penalty scores its compact class in the general form (three table loads per pair, no
+ * streamed values: the route of every penalised set before the marks moved into the memo bodies), 22 = 1: delta maintenance by one-block launches only (default: multi-block
  * above 3,000 records). Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */
 /* Ablation 8 (knob 3 = 8) of the last evaluation of paired read set rs: 8 wall-clock stamps (10 ns units) per wave,
  * [kernel entry, tables in LDS, records in, occurrences in, memo in, stores issued, block reduced, class]. Returns the
