@@ -219,6 +219,9 @@ def _load():
         L.gaml_hip_debug_occ_route.argtypes = [vp, C.c_int, _i64p]
     if hasattr(L, "gaml_hip_debug_occ_check"):  # development build only
         L.gaml_hip_debug_occ_check.argtypes = [vp, C.c_int, _i64p]
+    if hasattr(L, "gaml_hip_debug_batch_bad_bases"):  # development build only
+        L.gaml_hip_debug_batch_bad_bases.argtypes = [vp, C.c_int, C.c_void_p, C.c_int32]
+        L.gaml_hip_debug_batch_bad_bases.restype = C.c_int32
     if hasattr(L, "gaml_hip_shm_exchange_open"):
         L.gaml_hip_shm_exchange_open.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
         L.gaml_hip_shm_allreduce_sum.argtypes = [vp, C.c_void_p, C.c_int32]
@@ -856,6 +859,13 @@ class Context:
         if rc != 0 and res["compared"] == 0:
             self._check(rc)
         return res
+
+    def debug_batch_bad_bases(self, rs):
+        """bad_bases of paired set rs for every path set of the last calc_prob_batch, in its order (development build)."""
+        n = self._check(_lib.gaml_hip_debug_batch_bad_bases(self._h, rs, None, 0))
+        out = np.zeros(max(1, n), np.int64)
+        self._check(_lib.gaml_hip_debug_batch_bad_bases(self._h, rs, out.ctypes.data, n))
+        return out[:n].tolist()
 
     def debug_tables_check(self, rs):
         """The device table build against the host restatement, entry by entry (development build)."""

@@ -317,6 +317,13 @@ struct PairedSet {
   int last_blocks[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // partials written per path set of the last launch(es)
   bool last_host_partials = false;
   DevBuf probs, tabs, cov_bits, bad;
+  // gaml_hip_calc_prob_batch over a set with a coverage penalty: per launch [kMaxSets 64-bit counters | the bitmaps of its path
+  // sets], the launches of a chunk one behind the other (cov_multi_used: a launch never shares a bitmap with one in flight);
+  // store_bad_multi_kernel hands the counters over to h_bad[set's number in the chunk]
+  DevBuf cov_multi;
+  size_t cov_multi_used = 0;
+  PinBuf h_bad;
+  std::vector<int64_t> batch_bad;     // bad_bases per path set of the last gaml_hip_calc_prob_batch (gaml_hip_debug_batch_bad_bases)
   Arena arena;                        // per-call tables (occurrence images, thresholds, coverage layout): ring, whole tables per call
   // Blocking calls on a large-BAR device keep ONE resident copy of the tables and patch it in place (the kernel
   // of the previous call is done when the call returns): a call that shares most paths with the previous one writes

@@ -390,3 +390,11 @@ int gaml_hip_debug_occ_check(gaml_hip_ctx* c, int rs, int64_t* out4) {
   if (out4[2] || out4[3]) return fail(c, GAML_HIP_ESTATE, "device occurrence tables differ from the host image");
   return GAML_HIP_OK;
 }
+
+int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* c, int rs, int64_t* out, int32_t cap) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1 || cap < 0 || (cap > 0 && !out)) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const std::vector<int64_t>& b = c->paireds[c->handles[rs].idx]->batch_bad;
+  for (size_t k = 0; k < b.size() && k < (size_t)cap; k++) out[k] = b[k];
+  return (int32_t)b.size();
+}

@@ -516,7 +516,7 @@ void gaml_hip_destroy(gaml_hip_ctx* c) {
                                     s->dl_rec[m].release(); s->sp_rng[m].release(); s->sp_rec[m].release(); }
       s->dl_slot.release(); s->dl_spill.release(); s->sp_slot.release(); s->dstate.release(); s->dl_bins.release(); s->dl_bin_count.release(); s->dl_blk_tot.release(); s->dl_wlist.release(); s->h_dstate.release(); s->lcode.release(); s->len_combo_dev.release(); s->combo_tabs.release(); s->memo.release();
       drop_stage(s->stage_pool); s->h_part_sum.release(); s->h_part_zero.release(); s->h_timeline.release();
-      s->probs.release(); s->tabs.release(); s->arena.release(); s->persist.release(); s->occdev.release(); s->cov_bits.release(); s->bad.release(); if (s->ev_tables) (void)hipEventDestroy(s->ev_tables); if (s->ev_ovf) (void)hipEventDestroy(s->ev_ovf);
+      s->probs.release(); s->tabs.release(); s->arena.release(); s->persist.release(); s->occdev.release(); s->cov_bits.release(); s->bad.release(); s->cov_multi.release(); s->h_bad.release(); if (s->ev_tables) (void)hipEventDestroy(s->ev_tables); if (s->ev_ovf) (void)hipEventDestroy(s->ev_ovf);
       s->red.release(); s->adv.release();
     }
     for (auto& s : c->pacbios) { s->d_lens.release(); s->rec_off.release(); s->rec_walk.release(); s->rec_logp.release(); s->walk_count.release(); s->logprobs.release(); s->red.release(); drop_stage(s->stage);
@@ -1248,7 +1248,7 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* c, int32_t n_sets, const int32_t* pat
   if (c->device < 0) return fail(c, GAML_HIP_ENODEVICE, "scoring needs a HIP device: this context is host-only");
   if (n_sets == 0) return GAML_HIP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  for (auto& ps : c->paireds) paired_images_refresh(*ps);  // the batch routes patch the images from the current set's
+  for (auto& ps : c->paireds) { paired_images_refresh(*ps); ps->batch_bad.clear(); }  // the batch routes patch the images from the current set's
   const size_t ns = std::max<size_t>(1, c->handles.size());
   for (int32_t i = 0; i < n_sets; i++) if (set_offs[i + 1] < set_offs[i]) return fail(c, GAML_HIP_EINVAL, "set offsets must not decrease");
   int32_t done_sets = 0;
@@ -1293,6 +1293,12 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* c, int32_t n_sets, const int32_t* pat
   HIP_TRY(c, hipMemcpyAsync(c->batch_host.p, c->batch_dev.p, doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const double* res = (const double*)c->batch_host.p;
+  {
+    auto order = scoring_order(c);
+    for (int32_t i = 0; i < n_sets; i++)
+      for (size_t k = 0; k < order.size(); k++)
+        if (order[k].kind == 1) c->paireds[order[k].idx]->batch_bad.push_back((int64_t)res[(size_t)i * 4 * ns + 4 * k + 2]);
+  }
   for (int32_t i = 0; i < n_sets; i++) {
     if (int e = combine(c, res + (size_t)i * 4 * ns, &probs_out[i], zeros_out ? zeros_out + (size_t)i * 2 * ns : nullptr, tls[i])) return e;
     if (total_lens_out) total_lens_out[i] = tls[i];

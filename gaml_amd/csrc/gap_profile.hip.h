@@ -103,6 +103,9 @@ bool gap_device_capable(const gaml_hip_ctx* c) {
   if (c->multi || c->comm || c->device < 0 || c->world != 1 || c->peers != 1) return false;
   if (KNOB(c, 18) == 1) return false;  // knob 18 = 1: the fallback route (A/B, tests)
   if (!c->direct_write || KNOB(c, 8) != 0 || KNOB(c, 13) != 0) return false;
+  // a set with a coverage penalty: gap_tables_kernel moves table entries, not the set's coverage layout -- such a context
+  // searches through the fallback (whose multi-length steps are batches, one pass each)
+  for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0) return false;
   return batch_fast_capable(c);
 }
 

@@ -593,6 +593,10 @@ struct GenOut { double add; int zeros; };
 __device__ GenOut compact_general_call(unsigned long long kernargs, int i, int set);
 // table pair of class 1 / 2 at slot i (dj < 0) or delta pair dj at slot i; lds: room for 2 * kGenCands candidates, or null
 __device__ GenOut general_pair_call(unsigned long long kernargs, int i, int dj, int set, int4* lds);
+// the same for a multi-set launch that marks coverage (paired_score_multi_kernel<.., COV>): the set's view carries its bitmap
+// and slot_base table. Copies of their own, so that the callees of every other launch stay what they were.
+__device__ GenOut compact_general_call_cov(unsigned long long kernargs, int i, int set);
+__device__ GenOut general_pair_call_cov(unsigned long long kernargs, int i, int dj, int set, int4* lds);
 __device__ __forceinline__ unsigned long long kernel_args_address() {
 #if defined(__HIP_DEVICE_COMPILE__)
   return (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
@@ -717,6 +721,14 @@ __device__ __forceinline__ void cover_marks(const PairedArgs& a, uint2 r1, uint2
   const int base = a.path_base[(o1.y >> 16) & 0x7fffu];
   mark_bit(a.cov_bits, base + max(x, y));
   mark_bit(a.cov_bits, base + min(x, y));
+}
+// the same into the bitmap of one path set of a multi-set launch (SetDev::cov_bits / slot_base)
+__device__ __forceinline__ void cover_marks_set(uint32_t* bits, const int* slot_base, uint2 r1, uint2 r2, uint2 o1, uint2 o2) {
+  const int p1 = (int)(__funnelshift_r(r1.x, r1.y, 24) & 0xfffffffu), p2 = (int)(__funnelshift_r(r2.x, r2.y, 24) & 0xfffffffu);
+  const int x = p1 + (int)o1.x, y = p2 + (int)o2.x;
+  const int base = slot_base[(o1.y >> 16) & 0x7fffu];
+  mark_bit(bits, base + max(x, y));
+  mark_bit(bits, base + min(x, y));
 }
 // compact_prep without branches, on the 32-bit halves of the 8-byte record / occurrence words (the scoring kernel
 // is issue-bound at cfg3: the branchy 64-bit form was 156 instructions per pair, a third of a wave's lifetime)
@@ -1590,6 +1602,10 @@ struct SetDev {  // what differs between the path sets of one batch
   double two_T, log_two_T;
   double* part_sum;                // this set's per-block partials
   int* part_zero;
+  // a set with a coverage penalty: its own bitmap (a region of the launch's buffer at a 32-bit-aligned offset) and its own
+  // slot_base table -- PairedArgs::cov_bits / path_base of a single call; null for a set without penalty
+  uint32_t* cov_bits;
+  const int* slot_base;
 };
 // chg[mt][w]: bit s set = window w's table entry in set s of this launch may differ from set 0's (s >= 1; a batch whose
 // sets' tables were built from patches knows, batch_tables_kernel). A pair none of whose records touch such a window
@@ -1600,8 +1616,12 @@ struct SetDev {  // what differs between the path sets of one batch
 struct MultiSets { int n; int pad_; const unsigned char* chg[2]; SetDev set[kMaxSets]; };
 
 constexpr int kTfCodes = 16;  // length codes whose per-set thresholds a multi-set block keeps in LDS
+// COV: the launch marks coverage -- the set's bitmap and slot_base table travel too (pair_term, compact_cover and the general
+// paths then mark into this set's bitmap); without it the view is what it always was
+template <bool COV = false>
 __device__ __forceinline__ PairedArgs with_set(const PairedArgs& a, const SetDev& sd, const double* tfloor_lds = nullptr) {
   PairedArgs b = a;
+  if (COV) { b.cov_bits = sd.cov_bits; b.path_base = sd.slot_base; }
 #pragma unroll
   for (int mt = 0; mt < 2; mt++) { b.m[mt].occ12 = sd.occ12[mt]; b.occ12[mt] = sd.occ12[mt]; b.m[mt].multi_off = sd.multi_off[mt]; b.m[mt].multi = sd.multi[mt]; }
   b.tfloor_c = tfloor_lds ? tfloor_lds : sd.tfloor_c; b.tfloor0 = sd.tfloor0; b.two_T = sd.two_T; b.log_two_T = sd.log_two_T;
@@ -1612,23 +1632,27 @@ __device__ __forceinline__ PairedArgs with_set(const PairedArgs& a, const SetDev
 // the kernel's argument block, read where it is needed (a callee's view of it); a multi-set launch's: {PairedArgs, MultiSets}
 struct MultiKernArgs { PairedArgs a; MultiSets ms; };
 #if defined(__HIP_DEVICE_COMPILE__)
-#define GAML_CALLEE_ARGS(name, set)                                                                                                  \
+#define GAML_CALLEE_ARGS(name, set, COV)                                                                                             \
   const unsigned long long name##_u = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(kernargs >> 32)) << 32) |  \
                                       (unsigned)__builtin_amdgcn_readfirstlane((int)kernargs); /* (uniform: scalar loads) */         \
   const __attribute__((address_space(4))) MultiKernArgs* name##_p = (const __attribute__((address_space(4))) MultiKernArgs*)name##_u; \
   const PairedArgs name##_0 = name##_p->a;                                                                                           \
-  const PairedArgs name = (set) >= 0 ? with_set(name##_0, name##_p->ms.set[set]) : name##_0;
+  const PairedArgs name = (set) >= 0 ? with_set<COV>(name##_0, name##_p->ms.set[set]) : name##_0;
 #else
-#define GAML_CALLEE_ARGS(name, set) const PairedArgs& name = *(const PairedArgs*)nullptr;
+#define GAML_CALLEE_ARGS(name, set, COV) const PairedArgs& name = *(const PairedArgs*)nullptr;
 #endif
-__device__ __noinline__ GenOut compact_general_call(unsigned long long kernargs, int i, int set) {
-  GAML_CALLEE_ARGS(a, set)
+template <bool COV>
+__device__ __forceinline__ GenOut compact_general_impl(unsigned long long kernargs, int i, int set) {
+  GAML_CALLEE_ARGS(a, set, COV)
   GenOut o{0.0, 0};
   compact_general(a, i, o.add, o.zeros);
   return o;
 }
-__device__ __noinline__ GenOut general_pair_call(unsigned long long kernargs, int i, int dj, int set, int4* lds) {
-  GAML_CALLEE_ARGS(a, set)
+__device__ __noinline__ GenOut compact_general_call(unsigned long long kernargs, int i, int set) { return compact_general_impl<false>(kernargs, i, set); }
+__device__ __noinline__ GenOut compact_general_call_cov(unsigned long long kernargs, int i, int set) { return compact_general_impl<true>(kernargs, i, set); }
+template <bool COV>
+__device__ __forceinline__ GenOut general_pair_impl(unsigned long long kernargs, int i, int dj, int set, int4* lds) {
+  GAML_CALLEE_ARGS(a, set, COV)
   GenOut o{0.0, 0};
   int4 priv[2 * kGenCands];
   int4* const cand = lds ? lds : priv;
@@ -1656,10 +1680,14 @@ __device__ __noinline__ GenOut general_pair_call(unsigned long long kernargs, in
   }
   return o;
 }
+__device__ __noinline__ GenOut general_pair_call(unsigned long long kernargs, int i, int dj, int set, int4* lds) { return general_pair_impl<false>(kernargs, i, dj, set, lds); }
+__device__ __noinline__ GenOut general_pair_call_cov(unsigned long long kernargs, int i, int dj, int set, int4* lds) { return general_pair_impl<true>(kernargs, i, dj, set, lds); }
 
 // paired_compact4_body with the path sets in the inner loop. acc_s / acc_z: one running sum per (set, thread) in LDS
 // (a lane may take several rounds of four pairs; registers cannot be indexed by the set number).
-template <bool GEN, bool ONE>
+// COV: a launch of penalised sets -- a pair whose term clears the threshold marks both its ends in THIS set's bitmap, where
+// paired_compact4_body<.., COV> marks them in the call's.
+template <bool GEN, bool ONE, bool COV = false>
 __device__ __forceinline__ void paired_compact4_multi_body(const PairedArgs& a, const MultiSets& ms, const SlotRange rg, double* acc_s, int* acc_z, const double* tf) {
   const unsigned stride = (unsigned)rg.blocks * kBlock, n0 = (unsigned)rg.hi;  // (n0: end of this part's slots)
   const char* const rec0 = (const char*)a.rec8[0];
@@ -1668,6 +1696,7 @@ __device__ __forceinline__ void paired_compact4_multi_body(const PairedArgs& a, 
   char* const probs = (char*)a.probs;
   const uint32_t l12_one = ONE ? a.len_combo[0] : 0u;
   const double logfloor_one = ONE ? a.logfloor_c[0] : 0.0;
+  const double covthr_one = COV && ONE ? a.covthr0 : 0.0;
   for (unsigned base = (unsigned)rg.lo + (unsigned)rg.lb * kBlock + threadIdx.x; base < n0; base += 4 * stride) {
     uint2 r1[4], r2[4];
     unsigned lc[4];
@@ -1709,10 +1738,12 @@ __device__ __forceinline__ void paired_compact4_multi_body(const PairedArgs& a, 
       double lsum = 0.0;
       int zeros = 0;
       bool other = false;
+      unsigned mark_bits = 0;
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         double* const out = (double*)(probs + (base + k * stride) * 8u);
         if (state[k] >= 0) {
+          if (COV) mark_bits |= (unsigned)(m[k].x > (ONE ? covthr_one : a.covthr_c[lc[k]])) << k;
           if (last_set) __builtin_nontemporal_store(m[k].x, out);
           const bool floored = m[k].x < (ONE ? tfloor_one : tfs[lc[k]]);
           lsum += floored ? (ONE ? logfloor_one : a.logfloor_c[lc[k]]) : m[k].y - log2T;
@@ -1723,8 +1754,13 @@ __device__ __forceinline__ void paired_compact4_multi_body(const PairedArgs& a, 
           lsum += ONE ? logfloor_one : a.logfloor_c[kPairZero - state[k]];
         } else other |= state[k] == kPairOther && !((skip_bits >> k) & 1u);
       }
+      if (COV) {  // behind the set's sums and stores, as in the single-set body
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if ((mark_bits >> k) & 1u) cover_marks_set(sd.cov_bits, sd.slot_base, r1[k], r2[k], o1[k], o2[k]);
+      }
       if (__any(other)) {  // scores, but outside the memo: from the tables (rare)
-        const PairedArgs b = with_set(a, sd, tf ? tfs : nullptr);
+        const PairedArgs b = with_set<COV>(a, sd, tf ? tfs : nullptr);
 #pragma unroll 1
         for (int k = 0; k < 4; k++) {
           if (state[k] != kPairOther || ((skip_bits >> k) & 1u)) continue;
@@ -1743,7 +1779,7 @@ __device__ __forceinline__ void paired_compact4_multi_body(const PairedArgs& a, 
       if (GEN && __any(skip_bits != 0)) {  // as paired_compact4_body
 #pragma unroll 1
         for (int k = 0; k < 4; k++)
-          if ((skip_bits >> k) & 1u) { const GenOut o = compact_general_call(kernel_args_address(), (int)(base + k * stride), s); lsum += o.add; zeros += o.zeros; }
+          if ((skip_bits >> k) & 1u) { const GenOut o = COV ? compact_general_call_cov(kernel_args_address(), (int)(base + k * stride), s) : compact_general_call(kernel_args_address(), (int)(base + k * stride), s); lsum += o.add; zeros += o.zeros; }
       }
       acc_s[s * kBlock + threadIdx.x] += lsum;
       acc_z[s * kBlock + threadIdx.x] += zeros;
@@ -1755,7 +1791,7 @@ __device__ __forceinline__ void paired_compact4_multi_body(const PairedArgs& a, 
 // (the per-set arithmetic above goes records -> occurrence entries -> memo index -> memo entry, two dependent trips per set;
 // here a set costs one: its occurrence entries). Lanes, pairs, the values added and their order are the single-set
 // kernel's: a batch gives bit for bit what the sets give one by one.
-template <bool GEN, bool ONE>
+template <bool GEN, bool ONE, bool COV = false>
 __device__ __forceinline__ void paired_static4_multi_body(const PairedArgs& a, const MultiSets& ms, const SlotRange rg, double* acc_s, int* acc_z, const double* tf) {
   const unsigned stride = (unsigned)rg.blocks * kBlock, n0 = (unsigned)rg.hi;
   const char* const rec0 = (const char*)a.rec8[0];
@@ -1763,6 +1799,7 @@ __device__ __forceinline__ void paired_static4_multi_body(const PairedArgs& a, c
   const char* const sval = (const char*)a.static_val;
   char* const probs = (char*)a.probs;
   const double logfloor_one = ONE ? a.logfloor_c[0] : 0.0;
+  const double covthr_one = COV && ONE ? a.covthr0 : 0.0;
   for (unsigned base = (unsigned)rg.lo + (unsigned)rg.lb * kBlock + threadIdx.x; base < n0; base += 4 * stride) {
     uint2 r1[4], r2[4];
     double2 m[4];
@@ -1791,7 +1828,7 @@ __device__ __forceinline__ void paired_static4_multi_body(const PairedArgs& a, c
       }
       double lsum = acc_s[s * kBlock + threadIdx.x];  // (the running sum of this lane and set: additions in the single-set kernel's order)
       int zeros = acc_z[s * kBlock + threadIdx.x];
-      unsigned skip_bits = 0;
+      unsigned skip_bits = 0, mark_bits = 0;
 #pragma unroll
       for (int k = 0; k < 4; k++) {  // as paired_static4_body, statement for statement
         const bool none1 = r1[k].y == ~0u, none2 = r2[k].y == ~0u;
@@ -1815,11 +1852,17 @@ __device__ __forceinline__ void paired_static4_multi_body(const PairedArgs& a, c
         lsum += add;
         zeros += (int)floored;
         if (counted && last_set) __builtin_nontemporal_store(t, (double*)(probs + (base + k * stride) * 8u));
+        if (COV) mark_bits |= (unsigned)(scores & (t > (ONE ? covthr_one : a.covthr_c[lc[k]]))) << k;
+      }
+      if (COV) {  // behind the set's sums and stores, into this set's bitmap
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if ((mark_bits >> k) & 1u) cover_marks_set(sd.cov_bits, sd.slot_base, r1[k], r2[k], o1[k], o2[k]);
       }
       if (GEN && __any(skip_bits != 0)) {  // as paired_static4_body
 #pragma unroll 1
         for (int k = 0; k < 4; k++)
-          if ((skip_bits >> k) & 1u) { const GenOut o = compact_general_call(kernel_args_address(), (int)(base + k * stride), s); lsum += o.add; zeros += o.zeros; }
+          if ((skip_bits >> k) & 1u) { const GenOut o = COV ? compact_general_call_cov(kernel_args_address(), (int)(base + k * stride), s) : compact_general_call(kernel_args_address(), (int)(base + k * stride), s); lsum += o.add; zeros += o.zeros; }
       }
       acc_s[s * kBlock + threadIdx.x] = lsum;
       acc_z[s * kBlock + threadIdx.x] = zeros;
@@ -1830,7 +1873,7 @@ __device__ __forceinline__ void paired_static4_multi_body(const PairedArgs& a, c
 // Classes 1 and 2 with the path sets in the inner loop (paired_regs_body's pairs, lane -> pair mapping and order of
 // additions): records once, set 0 resolved and captured, later sets finished from the capture unless one of the
 // pair's windows changed.
-template <int K, bool GEN>
+template <int K, bool GEN, bool COV = false>
 __device__ __forceinline__ void paired_regs_multi_body(const PairedArgs& a, const MultiSets& ms, int lb, int slot_lo, int slot_hi, int block_lo,
                                                        int block_hi, double* acc_s, int* acc_z, const double* tf) {
   for (int i = slot_lo + (lb - block_lo) * kBlock + threadIdx.x; i < slot_hi; i += (block_hi - block_lo) * kBlock) {
@@ -1849,7 +1892,7 @@ __device__ __forceinline__ void paired_regs_multi_body(const PairedArgs& a, cons
     bool general = false;
 #pragma unroll 1
     for (int s = 0; s < ms.n; s++) {
-      const PairedArgs b = with_set(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
+      const PairedArgs b = with_set<COV>(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
       double lsum = acc_s[s * kBlock + threadIdx.x];
       int zeros = acc_z[s * kBlock + threadIdx.x];
       if (s == 0 || ((chg >> s) & 1u)) {
@@ -1861,7 +1904,7 @@ __device__ __forceinline__ void paired_regs_multi_body(const PairedArgs& a, cons
       } else {
         finish_val(b, i, val, s == ms.n - 1, lsum, zeros);
       }
-      if (GEN && general) { const GenOut o = general_pair_call(kernel_args_address(), i, -1, s, nullptr); lsum += o.add; zeros += o.zeros; }  // (in every set: val holds nothing of such a pair)
+      if (GEN && general) { const GenOut o = COV ? general_pair_call_cov(kernel_args_address(), i, -1, s, nullptr) : general_pair_call(kernel_args_address(), i, -1, s, nullptr); lsum += o.add; zeros += o.zeros; }  // (in every set: val holds nothing of such a pair)
       acc_s[s * kBlock + threadIdx.x] = lsum;
       acc_z[s * kBlock + threadIdx.x] = zeros;
     }
@@ -1869,7 +1912,7 @@ __device__ __forceinline__ void paired_regs_multi_body(const PairedArgs& a, cons
 }
 
 // paired_delta_body with the path sets in the inner loop
-template <bool GEN>
+template <bool GEN, bool COV = false>
 __device__ __forceinline__ void paired_delta_multi_body(const PairedArgs& a, const MultiSets& ms, int db, int delta_blocks, double* acc_s, int* acc_z, const double* tf) {
   for (int dj = db * kBlock + threadIdx.x; dj < a.dstate[kDsDirty]; dj += delta_blocks * kBlock) {
     const int i = a.dirty_slots[dj];
@@ -1891,7 +1934,7 @@ __device__ __forceinline__ void paired_delta_multi_body(const PairedArgs& a, con
     bool general = false;  // as resolved last: a set whose tables agree with its predecessor's on this pair's windows inherits it
 #pragma unroll 1
     for (int s = 0; s < ms.n; s++) {
-      const PairedArgs b = with_set(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
+      const PairedArgs b = with_set<COV>(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
       double lsum = acc_s[s * kBlock + threadIdx.x];
       int zeros = acc_z[s * kBlock + threadIdx.x];
       if (!mine) {
@@ -1905,7 +1948,7 @@ __device__ __forceinline__ void paired_delta_multi_body(const PairedArgs& a, con
       } else {
         finish_val(b, i, val, s == ms.n - 1, lsum, zeros);
       }
-      if (GEN && mine && general) { const GenOut o = general_pair_call(kernel_args_address(), i, dj, s, nullptr); lsum += o.add; zeros += o.zeros; }
+      if (GEN && mine && general) { const GenOut o = COV ? general_pair_call_cov(kernel_args_address(), i, dj, s, nullptr) : general_pair_call(kernel_args_address(), i, dj, s, nullptr); lsum += o.add; zeros += o.zeros; }
       acc_s[s * kBlock + threadIdx.x] = lsum;
       acc_z[s * kBlock + threadIdx.x] = zeros;
     }
@@ -1923,6 +1966,7 @@ __device__ __forceinline__ unsigned wave_changed(const Src& src, const unsigned 
 }
 
 // paired_overflow_body with the path sets in the inner loop: wave w keeps its running sums per set in acc (lane 0's)
+template <bool COV = false>
 __device__ __forceinline__ void paired_overflow_multi_body(const PairedArgs& a, const MultiSets& ms, int ovf_block, int ovf_blocks,
                                                            int4 (*cand)[2][kOvfCap], double* acc_s, int* acc_z, const double* tf) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1956,7 +2000,7 @@ __device__ __forceinline__ void paired_overflow_multi_body(const PairedArgs& a, 
     if (ms.chg[0]) chg = table ? (wave_changed(t1, ms.chg[0], lane) | wave_changed(t2, ms.chg[1], lane)) : (wave_changed(l1, ms.chg[0], lane) | wave_changed(l2, ms.chg[1], lane));
     PairVal val{0.0, 0.0, 0, 0};
     for (int s = 0; s < ms.n; s++) {
-      const PairedArgs b = with_set(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
+      const PairedArgs b = with_set<COV>(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
       double lsum = 0.0;
       int zeros = 0;
       if (s == 0 || ((chg >> s) & 1u)) {  // wave-uniform
@@ -1971,7 +2015,11 @@ __device__ __forceinline__ void paired_overflow_multi_body(const PairedArgs& a, 
   }
 }
 
-template <bool GEN>
+// COV: every set of the launch has a coverage penalty (the read set has one) and a bitmap of its own (SetDev::cov_bits): class 0
+// marks from the memo / streamed-value bodies, everything else through the set's view (with_set<true>). The host runs such a
+// launch without the capture (MultiSets::chg null): a pair finished from its set-0 result would still have to mark in set s,
+// at positions that depend on set s's layout.
+template <bool GEN, bool COV = false>
 __global__ __launch_bounds__(kBlock, 5) void paired_score_multi_kernel(PairedArgs a, MultiSets ms) {
   __shared__ double sh_s[kBlock / 64];
   __shared__ int sh_z[kBlock / 64];
@@ -2005,23 +2053,31 @@ __global__ __launch_bounds__(kBlock, 5) void paired_score_multi_kernel(PairedArg
       // kernel's, and so are the values -- a static memo index is the index the per-call arithmetic arrives at)
       const SlotRange rg = compact_range(a, lb);
       // the static part streams its values like the single-set kernel (same condition as there: memo present, no coverage marks)
-      const bool stat = lb < a.blocks0a && a.memo && !a.cov_bits && a.static_val;
+      // (a penalised launch keeps streaming, as paired_score_kernel<.., COV> does)
+      const bool stat = lb < a.blocks0a && a.memo && (COV || !a.cov_bits) && a.static_val;
       if (a.n_codes == 1) {
-        if (stat) paired_static4_multi_body<GEN, true>(a, ms, rg, acc_s, acc_z, tf);
-        else paired_compact4_multi_body<GEN, true>(a, ms, rg, acc_s, acc_z, tf);
+        if (stat) paired_static4_multi_body<GEN, true, COV>(a, ms, rg, acc_s, acc_z, tf);
+        else paired_compact4_multi_body<GEN, true, COV>(a, ms, rg, acc_s, acc_z, tf);
       } else {
         __shared__ uint32_t sh_combo[256];
         __shared__ double sh_logfloor[256];
         for (int k = threadIdx.x; k < a.n_codes; k += kBlock) { sh_combo[k] = a.len_combo[k]; sh_logfloor[k] = a.logfloor_c[k]; }
+        const double* covthr_lds = nullptr;
+        if constexpr (COV) {  // the coverage thresholds per length code (per read set, not per path set): looked up once per pair and set
+          __shared__ double sh_covthr[256];
+          for (int k = threadIdx.x; k < a.n_codes; k += kBlock) sh_covthr[k] = a.covthr_c[k];
+          covthr_lds = sh_covthr;
+        }
         __syncthreads();
         PairedArgs b = a;
         b.len_combo = sh_combo; b.logfloor_c = sh_logfloor;
-        if (stat) paired_static4_multi_body<GEN, false>(b, ms, rg, acc_s, acc_z, tf);
-        else paired_compact4_multi_body<GEN, false>(b, ms, rg, acc_s, acc_z, tf);
+        if (COV) b.covthr_c = covthr_lds;
+        if (stat) paired_static4_multi_body<GEN, false, COV>(b, ms, rg, acc_s, acc_z, tf);
+        else paired_compact4_multi_body<GEN, false, COV>(b, ms, rg, acc_s, acc_z, tf);
       }
-    } else if (lb < a.blocks01) paired_regs_multi_body<2, GEN>(a, ms, lb, a.n0, a.n01, a.blocks0, a.blocks01, acc_s, acc_z, tf);
-    else if (lb < a.blocks012) paired_regs_multi_body<4, GEN>(a, ms, lb, a.n01, a.n_main, a.blocks01, a.blocks012, acc_s, acc_z, tf);
-    else paired_delta_multi_body<GEN>(a, ms, lb - a.blocks012, a.main_blocks - a.blocks012, acc_s, acc_z, tf);
+    } else if (lb < a.blocks01) paired_regs_multi_body<2, GEN, COV>(a, ms, lb, a.n0, a.n01, a.blocks0, a.blocks01, acc_s, acc_z, tf);
+    else if (lb < a.blocks012) paired_regs_multi_body<4, GEN, COV>(a, ms, lb, a.n01, a.n_main, a.blocks01, a.blocks012, acc_s, acc_z, tf);
+    else paired_delta_multi_body<GEN, COV>(a, ms, lb - a.blocks012, a.main_blocks - a.blocks012, acc_s, acc_z, tf);
     for (int s = 0; s < ms.n; s++) {
       double lsum = acc_s[s * kBlock + threadIdx.x];
       int zeros = acc_z[s * kBlock + threadIdx.x];
@@ -2039,7 +2095,7 @@ __global__ __launch_bounds__(kBlock, 5) void paired_score_multi_kernel(PairedArg
   int* acc_z = (int*)(sh_raw + kCandBytes + kMaxSets * (kBlock / 64) * 8);
   if (threadIdx.x < kMaxSets * (kBlock / 64)) { acc_s[threadIdx.x] = 0.0; acc_z[threadIdx.x] = 0; }
   __syncthreads();
-  paired_overflow_multi_body(a, ms, lb - a.main_blocks, a.total_blocks - a.main_blocks, (int4(*)[2][kOvfCap])sh_raw, acc_s, acc_z, tf);
+  paired_overflow_multi_body<COV>(a, ms, lb - a.main_blocks, a.total_blocks - a.main_blocks, (int4(*)[2][kOvfCap])sh_raw, acc_s, acc_z, tf);
   __syncthreads();
   for (int s = 0; s < ms.n; s++) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2069,8 +2125,9 @@ struct CovArgs {
   unsigned long long* bad;  // out
 };
 
-__global__ __launch_bounds__(kBlock) void coverage_sweep_kernel(CovArgs a) {
-  for (int w = blockIdx.x * kBlock + threadIdx.x; w < a.total_words; w += gridDim.x * kBlock) {
+// the words of one bitmap, strided over `blocks` blocks of which this is number `block`
+__device__ __forceinline__ void coverage_sweep_words(const CovArgs& a, int block, int blocks) {
+  for (int w = block * kBlock + threadIdx.x; w < a.total_words; w += blocks * kBlock) {
     uint32_t word = a.bits[w];
     if (!word) continue;
     // locate the path of this word (few paths: binary search)
@@ -2105,6 +2162,21 @@ __global__ __launch_bounds__(kBlock) void coverage_sweep_kernel(CovArgs a) {
     }
     if (local) atomicAdd(a.bad, local);
   }
+}
+
+__global__ __launch_bounds__(kBlock) void coverage_sweep_kernel(CovArgs a) { coverage_sweep_words(a, (int)blockIdx.x, (int)gridDim.x); }
+
+// The sweeps of all path sets of a multi-set launch in ONE dispatch: blocks [block_off[s], block_off[s + 1]) sweep set s's
+// bitmap into set s's counter (a set without a bit to sweep -- the empty assembly -- has no blocks: its counter stays 0).
+struct CovMultiArgs { int n; int block_off[kMaxSets + 1]; CovArgs set[kMaxSets]; };
+__global__ __launch_bounds__(kBlock) void coverage_sweep_multi_kernel(CovMultiArgs a) {
+  int s = 0;
+  while (s + 1 < a.n && (int)blockIdx.x >= a.block_off[s + 1]) s++;
+  coverage_sweep_words(a.set[s], (int)blockIdx.x - a.block_off[s], a.block_off[s + 1] - a.block_off[s]);
+}
+// ... and their counters to where the host reads them after its wait (mapped pinned memory), n <= kMaxSets
+__global__ void store_bad_multi_kernel(const unsigned long long* bad, unsigned long long* out, int n) {
+  if (blockIdx.x == 0 && (int)threadIdx.x < n) out[threadIdx.x] = bad[threadIdx.x];
 }
 
 // ---------------------------------------------------------------------------------------

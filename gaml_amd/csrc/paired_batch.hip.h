@@ -5,8 +5,9 @@
 // ---------------------------------------------------------------------------------------------------------
 // gaml_hip_calc_prob_batch, fast path: up to kMaxSets path sets in ONE pass over the records of every paired set
 // (paired_score_multi_kernel). The host plans the sets one after the other straight into consecutive regions of one
-// arena slot; then one launch per read set, one wait. Contexts with other kinds of read sets, a coverage penalty or
-// without a memo take the sequential path below (same results).
+// arena slot; then one launch per read set, one wait. Contexts with other kinds of read sets or without a memo take the
+// sequential path below (same results). A set with a coverage penalty goes along: its path sets mark into bitmaps of their
+// own, one sweep dispatch per launch (launch_paired_multi); the wait is then a real stream wait, one per chunk.
 // ---------------------------------------------------------------------------------------------------------
 static bool batch_fast_capable(const gaml_hip_ctx* c) {
   if (c->handles.empty() || KNOB(c, 11) == 1) return false;  // knob 11 = 1: force the sequential path (A/B, tools/)
@@ -30,6 +31,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     PairedLayout L; std::vector<PairedLayout> Ls; std::vector<PairedPrep> prep;
     std::vector<int> patch_off; size_t n_patches = 0;
     size_t tail_fixed = 0, chg_bytes[2] = {0, 0};
+    size_t cov_at = 0, cov_cap = 0;  // a penalised set: every region carries its set's coverage layout behind the tables, room for cov_cap ints
     size_t bw[2] = {0, 0};  // table entries per mate the batch's regions carry: the windows there are + room for those the batch itself adds (the resident copy's capacity is far larger)
     int launches = 0;
     std::vector<int32_t> touched[2];  // union of the changed entries: the resident copy follows after the batch
@@ -48,6 +50,20 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     }
     PerSet& r = per[i];
     r.stride = align16(P.bytes);
+    if (ps.cfg.penalty_constant > 0) {
+      // the layout [slot_base | path_base | start_off | starts] of the largest set (paired_cov_ints: slots there are or the batch
+      // may add, paths, one start per path entry at most), written through the BAR like the thresholds
+      size_t most = 0, all_paths = 0;
+      for (int k = 0; k < n; k++) {
+        const size_t np = (size_t)(set_offs[k + 1] - set_offs[k]);
+        const size_t entries = (size_t)(offs[set_offs[k + 1]] - offs[set_offs[k]]);
+        most = std::max(most, 2 * (np + 1) + entries + np);
+        all_paths += np;
+      }
+      r.cov_at = r.stride;
+      r.cov_cap = (size_t)std::max(1, ps.planner.slot_count()) + all_paths + most + 16;
+      r.stride = align16(r.cov_at + r.cov_cap * sizeof(int32_t));
+    }
     r.L.tfloor_off = P.off_tfloor;
     r.L.l0 = OccLayout{P.off_occ[0], P.off_lo[0], P.off_m[0], P.off_lo[1] /* unused */};
     r.L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.bytes};
@@ -110,20 +126,28 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     int64_t pending = 0;
     if (int e = eval_begin(c, paths, offs + set_offs[k], set_offs[k + 1] - set_offs[k], &pending)) return e;
     tls[k] = c->pending_total_len;
+    // pass 2 of EVERY read set before any of them may give the chunk up: eval_begin has diffed all planners against this set,
+    // and a planner left without its apply() would hand the route that takes over a diff its images never saw
+    for (size_t i = 0; i < nps; i++) prepare_paired_tables_host(c, *c->paireds[i], per[i].prep[(size_t)k]);
     for (size_t i = 0; i < nps; i++) {
       PairedSet& ps = *c->paireds[i];
       PerSet& r = per[i];
       const PairedSet::Persist& P = ps.persist;
-      prepare_paired_tables_host(c, ps, r.prep[(size_t)k]);
       OccImage* im = ps.image;
       bool ok = !im[0].changed_all && !im[1].changed_all && !im[0].lists_changed && !im[1].lists_changed;
       for (int mt = 0; mt < 2 && ok; mt++) ok = im[mt].occ12.size() <= r.bw[mt] && r.n_patches + im[mt].changed.size() <= kPatchCap;
+      if (ok && ps.cfg.penalty_constant > 0) ok = paired_cov_ints(r.prep[(size_t)k]) <= r.cov_cap;  // (the layout does not fit its room: the full-tables route)
       if (!ok) {
         if (getenv("GAML_HIP_TRACE_HOST"))
           fprintf(stderr, "batch set %d: not a patch (all %d %d, lists %d %d, windows %zu/%zu %zu/%zu, patches %zu + %zu + %zu)\n", k, (int)im[0].changed_all, (int)im[1].changed_all,
                   (int)im[0].lists_changed, (int)im[1].lists_changed, im[0].occ12.size(), P.cap_w[0], im[1].occ12.size(), P.cap_w[1], r.n_patches, im[0].changed.size(), im[1].changed.size());
         c->pending_open = false;
         return give_up(launched > 0);
+      }
+      if (ps.cfg.penalty_constant > 0) {  // this set's coverage layout into its region (fenced with the thresholds, arena_commit)
+        paired_cov_layout(r.prep[(size_t)k], r.cov_at, r.Ls[(size_t)k]);
+        r.Ls[(size_t)k].total = r.stride;
+        paired_cov_pack(r.prep[(size_t)k], r.Ls[(size_t)k], r.wp + (size_t)k * r.stride);
       }
       BatchPatch* dp = (BatchPatch*)(r.wp + r.stride * (size_t)n);
       for (int mt = 0; mt < 2; mt++) {
@@ -167,7 +191,10 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
         finisher_order_sum((const double*)ps.h_part_sum.p + (size_t)k * ps.host_part_stride, (const int*)ps.h_part_zero.p + (size_t)k * ps.host_part_stride,
                            ps.last_blocks[k], &out[0], &out[1]);
       out[3] = (double)ps.mate[0].n_local();
-      ps.last_bad_bases = 0;
+      // a penalised set: the launch's counters, handed over behind the partials (store_bad_multi_kernel)
+      if (ps.cfg.penalty_constant > 0 && ps.last_blocks[k] > 0) out[2] = (double)((const unsigned long long*)ps.h_bad.p)[k];
+      ps.batch_bad.push_back((int64_t)out[2]);
+      ps.last_bad_bases = (int64_t)out[2];
     }
   return 0;
 }
@@ -215,10 +242,10 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
     int64_t pending = 0;
     if (int e = eval_begin(c, paths, offs + set_offs[k], set_offs[k + 1] - set_offs[k], &pending)) return e;
     tls[k] = c->pending_total_len;
+    for (size_t i = 0; i < nps; i++) prepare_paired_tables_host(c, *c->paireds[i], per[i].prep[(size_t)k]);  // (all of them first: see batch_chunk_patched)
     for (size_t i = 0; i < nps; i++) {
       PairedSet& ps = *c->paireds[i];
       PairedPrep& p = per[i].prep[(size_t)k];
-      prepare_paired_tables_host(c, ps, p);
       bool fits = ps.mate[0].wins.size() <= per[i].cap_w[0] && ps.mate[1].wins.size() <= per[i].cap_w[1];
       if (fits) { per[i].L[(size_t)k] = paired_layout(ps, p, per[i].cap_w); fits = per[i].L[(size_t)k].total <= per[i].stride; }
       if (!fits) {  // the tables outgrew the region reserved per set: the sequential path takes this chunk (after what is in flight)
@@ -246,7 +273,10 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
         finisher_order_sum((const double*)ps.h_part_sum.p + (size_t)k * ps.host_part_stride, (const int*)ps.h_part_zero.p + (size_t)k * ps.host_part_stride,
                            ps.last_blocks[k], &out[0], &out[1]);
       out[3] = (double)ps.mate[0].n_local();
-      ps.last_bad_bases = 0;
+      // a penalised set: the launch's counters, handed over behind the partials (store_bad_multi_kernel)
+      if (ps.cfg.penalty_constant > 0 && ps.last_blocks[k] > 0) out[2] = (double)((const unsigned long long*)ps.h_bad.p)[k];
+      ps.batch_bad.push_back((int64_t)out[2]);
+      ps.last_bad_bases = (int64_t)out[2];
     }
   return 0;
 }

@@ -280,7 +280,7 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
       P.off_m[mt] = at; at = align16(at + P.cap_m[mt] * sizeof(OccQuad));
     }
     // (the coverage layout: a few ints per path and contig, written whole per call; room for many times the paths there are)
-    P.cap_cov = need_cov ? std::max<size_t>(4 * need_cov, 16384) : 0;
+    P.cap_cov = need_cov ? std::max<size_t>(4 * need_cov, 16384) : P.cap_cov;  // (a batch brings the copy up to date without a layout: the room stays)
     P.off_cov = at; at = align16(at + P.cap_cov * sizeof(int32_t));
     if (at > P.bytes) {
       HIP_TRY(c, hipStreamSynchronize(st));
@@ -342,6 +342,7 @@ void paired_persist_view(const PairedSet& s, int32_t total_len, SetDev& sd) {
   sd.tfloor0 = paired_tfloor0(s, sd.two_T);
   sd.log_two_T = std::log(sd.two_T);
   sd.part_sum = nullptr; sd.part_zero = nullptr;
+  sd.cov_bits = nullptr; sd.slot_base = nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -446,6 +447,7 @@ void paired_set_view(const PairedSet& s, const PairedLayout& L, const char* aren
   sd.tfloor0 = paired_tfloor0(s, sd.two_T);
   sd.log_two_T = std::log(sd.two_T);
   sd.part_sum = nullptr; sd.part_zero = nullptr;
+  sd.cov_bits = nullptr; sd.slot_base = nullptr;
 }
 
 void paired_apply_set(PairedArgs& a, const SetDev& sd) {
@@ -645,9 +647,15 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
 // ---------------------------------------------------------------------------------------------------------
 // several path sets, one pass over the records. The caller has planned every set (pass 1 + pass 2 + pack) into
 // consecutive regions of ONE arena slot: `arena` + k * stride, layouts L[k]. Blocking only (partials in pinned memory).
+// A set with a coverage penalty: every path set marks into a bitmap of its own (a region of PairedSet::cov_multi, cleared by
+// ONE memset per launch together with the sets' counters), its coverage layout sits in its arena region (L[k].sb_off ..);
+// behind the scoring launch one sweep dispatch for all sets and one that hands the counters to the host.
 // ---------------------------------------------------------------------------------------------------------
 bool paired_multi_capable(const gaml_hip_ctx* c, const PairedSet& s) {
-  return !(s.cfg.penalty_constant > 0) && KNOB(c, 3) == 0 && KNOB(c, 4) == 0 && s.floor_positive;
+  if (KNOB(c, 3) != 0 || KNOB(c, 4) != 0 || !s.floor_positive) return false;
+  // a penalised set: under the conditions of the single call's COV instantiation (knob 21 = 1, class 0 in its general form:
+  // the sequential path)
+  return !(s.cfg.penalty_constant > 0) || KNOB(c, 21) == 0;
 }
 
 // Sets [first, first + n_sets) of a batch (L / preps / total_lens / arena regions / partial regions are indexed by the
@@ -670,27 +678,82 @@ int launch_paired_multi(gaml_hip_ctx* c, PairedSet& s, int first, int n_sets, co
   s.last_sets = first + n_sets;
   if (n == 0) { for (int k = first; k < first + n_sets; k++) s.last_blocks[k] = 0; return 0; }
   if (int e = paired_host_partials(c, s, first, n_sets, n_partials, &d_sum, &d_zero)) return e;
+  const bool cov = s.cfg.penalty_constant > 0;
+  // this launch's part of cov_multi: [kMaxSets counters | bitmap of set first | ... ] -- behind the part of the chunk's
+  // earlier launch, which may still be in flight
+  size_t cov_off[kMaxSets], cov_bytes = 0;
+  char* cov_base = nullptr;
+  if (cov) {
+    cov_bytes = kMaxSets * sizeof(unsigned long long);
+    for (int k = 0; k < n_sets; k++) { cov_off[k] = cov_bytes; cov_bytes += std::max<size_t>(4, (size_t)preps[first + k].total_bits / 8); }
+    cov_bytes = (cov_bytes + 63) & ~(size_t)63;
+    if (first == 0) s.cov_multi_used = 0;
+    if (s.cov_multi_used + cov_bytes > s.cov_multi.cap) {  // grows only when a batch needs more than it holds
+      HIP_TRY(c, hipStreamSynchronize(st));
+      HIP_TRY(c, s.cov_multi.reserve(2 * (s.cov_multi_used + cov_bytes)));
+      s.cov_multi_used = 0;  // (nothing is in flight any more)
+    }
+    HIP_TRY(c, s.h_bad.reserve(kMaxSets * sizeof(unsigned long long)));
+    cov_base = s.cov_multi.as<char>() + s.cov_multi_used;
+    s.cov_multi_used += cov_bytes;
+    HIP_TRY(c, hipMemsetAsync(cov_base, 0, cov_bytes, st));
+  }
   MultiSets ms;
   memset(&ms, 0, sizeof(ms));
   ms.n = n_sets;
   if (KNOB(c, 11) >= 32) ms.pad_ = (KNOB(c, 11) - 32) & 31;  // timing experiments: leave out classes of blocks (bits: compact, <=2, <=4, delta, wave-per-pair)
-  if (chg && KNOB(c, 11) < 64) { ms.chg[0] = chg[0]; ms.chg[1] = chg[1]; }  // (>= 64: and every set resolves every pair)  // (which table entries differ between the sets: only a batch built from patches knows)
+  if (chg && KNOB(c, 11) < 64 && !cov) { ms.chg[0] = chg[0]; ms.chg[1] = chg[1]; }  // (a penalised launch runs without the capture: paired_score_multi_kernel)  // (>= 64: and every set resolves every pair)  // (which table entries differ between the sets: only a batch built from patches knows)
   for (int k = 0; k < n_sets; k++) {
     const int g = first + k;  // the set's number in the batch
     paired_set_view(s, L[g], arena + (size_t)g * stride, total_lens[g], ms.set[k]);
     ms.set[k].part_sum = d_sum + (size_t)g * s.host_part_stride;
     ms.set[k].part_zero = d_zero + (size_t)g * s.host_part_stride;
+    if (cov) {
+      ms.set[k].cov_bits = (uint32_t*)(cov_base + cov_off[k]);
+      ms.set[k].slot_base = (const int*)(arena + (size_t)g * stride + L[g].sb_off);  // by path slot
+    }
   }
   paired_apply_set(a, ms.set[0]);  // (fields every set overrides; harmless defaults)
+  if (cov) { a.cov_bits = ms.set[0].cov_bits; a.path_base = ms.set[0].slot_base; }
   std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
   if (c->event_timing && (c->event_tick++ % c->event_every) == 0) { if (int e = take_events(c, &ev)) return e; }
   hipEvent_t e0 = ev ? ev->first : nullptr, e1 = ev ? ev->second : nullptr;
   const dim3 grid(a.total_blocks), block(kBlock);
   // (any set with a window that occurs several times: the GEN instantiation for all of them -- a set without such a window
   // never takes its extra branches, its sums are those of the other instantiation)
-  if (any_set) hipExtLaunchKernelGGL((paired_score_multi_kernel<true>), grid, block, 0, st, e0, e1, 0, a, ms);
+  if (cov) {
+    if (any_set) hipExtLaunchKernelGGL((paired_score_multi_kernel<true, true>), grid, block, 0, st, e0, e1, 0, a, ms);
+    else hipExtLaunchKernelGGL((paired_score_multi_kernel<false, true>), grid, block, 0, st, e0, e1, 0, a, ms);
+  } else if (any_set) hipExtLaunchKernelGGL((paired_score_multi_kernel<true>), grid, block, 0, st, e0, e1, 0, a, ms);
   else hipExtLaunchKernelGGL((paired_score_multi_kernel<false>), grid, block, 0, st, e0, e1, 0, a, ms);
   HIP_TRY(c, hipGetLastError());
+  if (cov) {
+    CovMultiArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.n = n_sets;
+    unsigned long long* counters = (unsigned long long*)cov_base;
+    for (int k = 0; k < n_sets; k++) {
+      const int g = first + k;
+      const char* region = arena + (size_t)g * stride;
+      CovArgs& v = ca.set[k];
+      v.bits = ms.set[k].cov_bits;
+      v.path_base = (const int*)(region + L[g].pb_off);
+      v.start_off = (const int*)(region + L[g].so_off);
+      v.starts = (const int*)(region + L[g].st_off);
+      v.n_paths = preps[g].n_paths;
+      v.total_words = preps[g].total_bits / 32;
+      v.cov_move = s.cfg.step;
+      v.far = s.cfg.insert_mean + 5 * s.cfg.insert_std;
+      v.bad = counters + k;
+      ca.block_off[k + 1] = ca.block_off[k] + (v.total_words > 0 ? grid_for(v.total_words) : 0);  // (the empty assembly: no blocks, its counter stays 0)
+    }
+    if (ca.block_off[n_sets] > 0) {
+      hipLaunchKernelGGL(coverage_sweep_multi_kernel, dim3((unsigned)ca.block_off[n_sets]), dim3(kBlock), 0, st, ca);
+      HIP_TRY(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(store_bad_multi_kernel, dim3(1), dim3(64), 0, st, counters, (unsigned long long*)s.h_bad.dev + first, n_sets);
+    HIP_TRY(c, hipGetLastError());
+  }
   if (!c->event_timing || ev) {
     double rec = 0;
     for (int k = first; k < first + n_sets; k++) rec += (double)preps[k].assembled_records;

@@ -124,6 +124,12 @@ int gaml_hip_debug_occ_route(gaml_hip_ctx* ctx, int readset, int64_t* out6);
  * GAML_HIP_ESTATE when they differ. All zeros when the last call did not take the route. */
 int gaml_hip_debug_occ_check(gaml_hip_ctx* ctx, int readset, int64_t* out4);
 
+/* bad_bases of paired set `readset` for every path set of the last gaml_hip_calc_prob_batch, in the batch's order, whichever
+ * route its chunks took (0 for a set without coverage penalty). Returns the number of path sets; at most `cap` are written.
+ * A batch over penalised sets: knob 11 = 0 the one-pass routes (tables from patches, else whole; the capture of unchanged
+ * pairs is always off for such a launch, so 3 equals 0 there), 2 whole tables per set, 1 one call per path set. */
+int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* ctx, int readset, int64_t* out, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

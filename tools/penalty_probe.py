@@ -5,13 +5,16 @@ cfg3j as bench.py's `jumping` block sets it up): one JSON line.
      median, p90 and max, and the median of gaml_hip_last_phases -- the calls that share most paths with their predecessor
   b  the 8 rotating unrelated path sets of bench.py (every call a whole-set call), 400 calls
   c  200 gaml_hip_fix_gap_length searches at the sites tools/gap_probe.py uses (a penalised set: the fallback route, one
-     blocking call per evaluation)
+     blocking call per evaluation; its steps of 2-3 lengths are batches)
+  d  gaml_hip_calc_prob_batch: 200 batches of 8 single-edit candidates of the current assembly (synth.sa_move, 60 % of the
+     batches adopt one candidate), 100 batches of the 8 unrelated path sets of part b, and 100 batches each of the first
+     2, 3 and 4 candidates (the sizes of the gap fallback's steps): per batch and per candidate the median, p90 and max
 
 The library under test is whatever GAML_HIP_LIB / GAML_HIP_FLAVOUR select: run it alternately on two builds (for example a
 tools/build_variant.sh build of another commit), several rounds, and compare the medians of the rounds' medians against
 their spread between rounds.
 
-Usage: python tools/penalty_probe.py [--parts abc] [--steps 1000] [--searches 200] [--tag NAME]
+Usage: python tools/penalty_probe.py [--parts abcd] [--steps 1000] [--searches 200] [--tag NAME]
        rocprofv3 --kernel-trace --stats -d DIR -- python tools/penalty_probe.py --parts a
 """
 from __future__ import annotations
@@ -58,6 +61,7 @@ def main():
     ap.add_argument("--parts", default="abc")
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--searches", type=int, default=200)
+    ap.add_argument("--batches", type=int, default=200)
     ap.add_argument("--tag", default="")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
@@ -90,7 +94,7 @@ def main():
                         quiet_median_us=round(float(np.median([u for u, p in zip(us, ph) if p[2] < 1.0])), 2),  # calls that aligned no new window
                         value=ctx.score(fps[-1]), bad_bases=ctx.bad_bases(0), static_pairs=ctx.table_stats(0)["static_index_pairs"])
         ctx.close()
-    if "b" in a.parts or "c" in a.parts:
+    if "b" in a.parts or "c" in a.parts or "d" in a.parts:
         ctx = make()
     if "b" in a.parts:
         walk = synth.genome_walk(g)
@@ -133,6 +137,56 @@ def main():
         res["c"] = dict(stats(us), searches=len(us), evaluations_per_search=round(float(np.mean(evals)), 2),
                         us_per_evaluation=round(float(np.median(np.array(us) / np.maximum(1, evals))), 2),
                         lengths_sum=int(np.sum(lengths)), gap_stats=ctx.gap_stats())
+    if "d" in a.parts:
+        start, seq = synth.sa_sequence(g, 60)
+        base = seq[-1]
+        rng = np.random.default_rng(7)
+        batches, current = [], base
+        for _ in range(a.batches):
+            cands = [synth.sa_move(rng, current, g) for _ in range(8)]
+            batches.append(cands)
+            if rng.random() < 0.6:
+                current = cands[int(rng.integers(0, 8))]
+        walk = synth.genome_walk(g)
+        n = len(walk)
+        variants = [[list(walk)]]
+        for i in range(1, 8):  # bench.py path_variants
+            cut = (n * i) // 8
+            cut -= cut % 2
+            cut = max(1, min(n - 1, cut))
+            variants.append([list(walk[:cut]), list(walk[cut:])])
+        ctx.calc_prob(base)
+        for cands in batches:          # every window the candidates touch aligned
+            ctx.calc_prob_batch(cands)
+        ctx.calc_prob_batch(variants)
+        ctx.compact_tables()
+        ctx.calc_prob(base)
+
+        def run(lists):
+            bps = [api.BatchPaths(b) for b in lists]
+            us = []
+            for bp in bps:
+                t0 = time.perf_counter()
+                ctx.calc_prob_batch(bp)
+                us.append((time.perf_counter() - t0) * 1e6)
+            k = len(lists[0])
+            per = stats(np.asarray(us) / k)
+            return dict(stats(us), batches=len(us), sets=k, per_set_median_us=per["median_us"], per_set_p90_us=per["p90_us"], per_set_max_us=per["max_us"])
+
+        before = ctx.table_stats(0)
+        d = {"candidates": run(batches)}
+        ctx.calc_prob(variants[0])
+        run([variants] * 3)
+        d["unrelated"] = run([variants] * (a.batches // 2))
+        for k in (2, 3, 4):
+            ctx.calc_prob(base)
+            d["candidates_%d" % k] = run([b[:k] for b in batches[: a.batches // 2]])
+        after = ctx.table_stats(0)
+        d["batches_patched"] = after["batches_patched"] - before["batches_patched"]
+        d["batches_full"] = after["batches_full"] - before["batches_full"]
+        last = ctx.calc_prob_batch(batches[-1])
+        d["value"], d["bad_bases"] = last[-1][0], ctx.bad_bases(0)
+        res["d"] = d
     print(json.dumps(res))
 
 
