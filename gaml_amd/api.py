@@ -215,6 +215,8 @@ def _load():
         L.gaml_hip_debug_static_check.argtypes = [vp, C.c_int, _i64p]
     if hasattr(L, "gaml_hip_debug_set_knob"):  # development build only
         L.gaml_hip_debug_set_knob.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "gaml_hip_debug_aligner_routes"):  # development build only
+        L.gaml_hip_debug_aligner_routes.argtypes = [vp, _i64p]
     if hasattr(L, "gaml_hip_debug_occ_route"):  # development build only
         L.gaml_hip_debug_occ_route.argtypes = [vp, C.c_int, _i64p]
     if hasattr(L, "gaml_hip_debug_occ_check"):  # development build only
@@ -841,6 +843,14 @@ class Context:
         self._check(_lib.gaml_hip_debug_static_check(self._h, rs, out))
         return {"static_pairs": int(out[0]), "other_pairs": int(out[1]), "violations": int(out[2]), "no_record": int(out[3]),
                 "different_windows": int(out[4]), "orientation": int(out[5]), "distance": int(out[6]), "edits_or_code": int(out[7])}
+
+    def debug_aligner_routes(self):
+        """The window aligner's rarely taken routes so far: repeated attempts of the general route (spans or candidates did
+        not fit), paired small batches handed to the per-mate route (candidates did not fit / the device filing refused
+        them), batches flushed to the host aligner after the sixth attempt (development build)."""
+        out = np.zeros(4, np.int64)
+        self._check(_lib.gaml_hip_debug_aligner_routes(self._h, out))
+        return {"retries": int(out[0]), "pair_capacity": int(out[1]), "pair_filing": int(out[2]), "flushed": int(out[3])}
 
     def debug_occ_route(self, rs):
         """Whole-set calls whose occurrence tables the device built / the host built / that were evaluated again on the

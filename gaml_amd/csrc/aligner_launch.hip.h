@@ -489,7 +489,7 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
   if (file_dev) {
     if (int e = aln_small_wait(c, S, job)) return e;
     const AlnFileOut* fo = (const AlnFileOut*)((const char*)S.out_host.p + 128);
-    if (fo->status != 0) return 1;  // not filed (too many hits for one block, more candidates than the buffers hold): the per-mate route redoes the batch
+    if (fo->status != 0) { ALN_ROUTE(c, 2); return 1; }  // not filed (too many hits for one block, more candidates than the buffers hold): the per-mate route redoes the batch
     nc = fo->n_cands;
     int64_t at[2] = {ps.dev[0].pool_n, ps.dev[1].pool_n};
     for (int k = 0; k < nw; k++) {
@@ -517,6 +517,7 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
     return 0;
   }
   const int rc = aln_small_collect(c, S, job, hits, &nc);
+  if (rc == 1) ALN_ROUTE(c, 1);
   if (rc != 0) return rc;  // 1: the candidates did not fit: the per-mate route redoes the batch
   const double t2 = now_us();
   if (timed) {
@@ -617,6 +618,7 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
   t1 = now_us();
   size_t cap_spans = std::max<size_t>(1 << 16, wstr.size());        // a span per window base and strand at most ~2x
   size_t cap_cands = std::max<size_t>(1 << 18, 8 * wstr.size());
+  if (KNOB(c, 23) > 0) cap_spans = cap_cands = (size_t)KNOB(c, 23);  // knob 23: first capacities (tests of the retry loop below)
   unsigned counts[2] = {0, 0};
   for (int attempt = 0; attempt < 6; attempt++) {
     HIP_TRY(c, S.spans.reserve(cap_spans * sizeof(AlnSpan)));
@@ -635,7 +637,8 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
     if (counts[0] <= cap_spans && counts[1] <= cap_cands) break;
     cap_spans = std::max<size_t>(cap_spans, (size_t)counts[0] + 16);
     cap_cands = std::max<size_t>(cap_cands, (size_t)counts[1] + 16);
-    if (attempt == 5) { m.flush_pending_cpu(c->g); return 0; }
+    if (attempt == 5) { ALN_ROUTE(c, 3); m.flush_pending_cpu(c->g); return 0; }
+    ALN_ROUTE(c, 0);
   }
   gpu_probe(st, c->warm_buf.p, "  spans + candidates done");
   t2 = now_us();

@@ -43,6 +43,14 @@
 #else
 #define KNOB(c, i) 0
 #endif
+// ... and so do the aligner's route counters (gaml_hip_debug_aligner_routes): 0 general-route retries, 1 / 2 paired small batches
+// handed to the per-mate route because the candidates did not fit / because the device filing refused them, 3 batches flushed
+// to the host aligner after the sixth attempt
+#ifdef GAML_HIP_DEV
+#define ALN_ROUTE(c, i) ((c)->aln_routes[i]++)
+#else
+#define ALN_ROUTE(c, i) ((void)0)
+#endif
 
 namespace gaml {
 namespace detail {
@@ -484,6 +492,7 @@ struct gaml_hip_ctx {
   double aln_us = 0;
   double aln_stage_us[5] = {0, 0, 0, 0, 0};  // window strings + upload, spans + candidates, extension, D2H of hits, sort + finalize
   int64_t aln_batches = 0;
+  int64_t aln_routes[4] = {0, 0, 0, 0};  // ALN_ROUTE: development builds only
   int knobs[24] = {0};  // tuning experiments and A/B switches (gaml_hip_debug.h), development builds only: read through KNOB()
   bool direct_write = false;  // large-BAR device: the host writes per-call tables straight into device memory (Arena)
   int32_t peers = 1;  // contexts (incl. this one) that hold reads of the same read sets: >1 => window maxima must be exchanged

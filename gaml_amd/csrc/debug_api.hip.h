@@ -361,6 +361,13 @@ int gaml_hip_debug_occ_route(gaml_hip_ctx* c, int rs, int64_t* out6) {
   return GAML_HIP_OK;
 }
 
+int gaml_hip_debug_aligner_routes(gaml_hip_ctx* c, int64_t* out4) {
+  MULTI_SHARD0(c);
+  if (!c || !out4) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  for (int k = 0; k < 4; k++) out4[k] = c->aln_routes[k];
+  return GAML_HIP_OK;
+}
+
 int gaml_hip_debug_occ_check(gaml_hip_ctx* c, int rs, int64_t* out4) {
   MULTI_SHARD0(c);
   if (!c || !out4 || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1) return fail(c, GAML_HIP_EINVAL, "bad arguments");

@@ -77,7 +77,8 @@ int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int
  * memo indices (takes effect at the next table build; same values either way), 20 = blocks of the compact class's second
  * part, 21 = 1: a set with a coverage penalty scores its compact class in the general form (three table loads per pair, no
  * streamed values: the route of every penalised set before the marks moved into the memo bodies), 22 = 1: delta maintenance by one-block launches only (default: multi-block
- * above 3,000 records). Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */
+ * above 3,000 records), 23 = n > 0: the window aligner's general route starts with room for n spans and n candidates instead of
+ * its estimate from the window bases (its retry loop then grows both; same records either way). Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */
 /* Ablation 8 (knob 3 = 8) of the last evaluation of paired read set rs: 8 wall-clock stamps (10 ns units) per wave,
  * [kernel entry, tables in LDS, records in, occurrences in, memo in, stores issued, block reduced, class]. Returns the
  * number of waves copied. Tuning aid (tools/kernel_timeline.py). */
@@ -123,6 +124,12 @@ int gaml_hip_debug_occ_route(gaml_hip_ctx* ctx, int readset, int64_t* out6);
  * built for the same set. out4 = {entries compared, entries present, mismatches, mates whose host image needs lists};
  * GAML_HIP_ESTATE when they differ. All zeros when the last call did not take the route. */
 int gaml_hip_debug_occ_check(gaml_hip_ctx* ctx, int readset, int64_t* out4);
+
+/* Which of its rarely taken routes the window aligner took so far (gaml_amd/csrc/aligner_launch.hip.h): out4 = {attempts of the
+ * general route repeated because the spans or candidates did not fit its buffers, paired small batches handed to the per-mate
+ * route because the candidates did not fit the fixed buffers, ... because the device filing refused them (more than 2,048
+ * candidates, pool full), batches flushed to the host aligner after the sixth attempt}. */
+int gaml_hip_debug_aligner_routes(gaml_hip_ctx* ctx, int64_t* out4);
 
 /* bad_bases of paired set `readset` for every path set of the last gaml_hip_calc_prob_batch, in the batch's order, whichever
  * route its chunks took (0 for a set without coverage penalty). Returns the number of path sets; at most `cap` are written.
