@@ -224,6 +224,11 @@ def _load():
     if hasattr(L, "gaml_hip_debug_batch_bad_bases"):  # development build only
         L.gaml_hip_debug_batch_bad_bases.argtypes = [vp, C.c_int, C.c_void_p, C.c_int32]
         L.gaml_hip_debug_batch_bad_bases.restype = C.c_int32
+    if hasattr(L, "gaml_hip_debug_delta_check"):  # development build only
+        L.gaml_hip_debug_delta_check.argtypes = [vp, C.c_int, _i64p]
+        L.gaml_hip_debug_delta_routes.argtypes = [vp, C.c_int, _i64p]
+        L.gaml_hip_debug_delta_numbering.argtypes = [vp, C.c_int, C.c_void_p, C.c_void_p, C.c_int32]
+        L.gaml_hip_debug_delta_numbering.restype = C.c_int32
     if hasattr(L, "gaml_hip_shm_exchange_open"):
         L.gaml_hip_shm_exchange_open.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
         L.gaml_hip_shm_allreduce_sum.argtypes = [vp, C.c_void_p, C.c_int32]
@@ -886,6 +891,34 @@ class Context:
         if rc != 0 and res["compared"] == 0:
             self._check(rc)
         return res
+
+    def debug_delta_check(self, rs):
+        """The live record tables plus the live delta lists against the host restatement, read by read; changes nothing
+        (development build). Raises only when nothing could be compared; a mismatch is reported in the result."""
+        out = np.zeros(12, np.int64)
+        rc = _lib.gaml_hip_debug_delta_check(self._h, rs, out)
+        res = {"on_lists": int(out[0]), "from_static": int(out[1]), "from_compact": int(out[2]), "from_two": int(out[3]), "from_four": int(out[4]),
+               "from_more": int(out[5]), "stride_2": int(out[6]), "stride_4": int(out[7]), "long_lists": int(out[8]), "compared": int(out[9]),
+               "mismatches": int(out[10]), "left_out": int(out[11]), "rc": int(rc)}
+        if rc != 0 and res["mismatches"] == 0:
+            self._check(rc)
+        return res
+
+    def debug_delta_routes(self, rs):
+        """The launches the delta maintenance chose so far (development build): one-block launches by records per thread,
+        multi-block launches, those with a device window list, windows cut across launches, records / windows of the last
+        maintenance call, the smallest block of a one-record-per-thread launch."""
+        out = np.zeros(10, np.int64)
+        self._check(_lib.gaml_hip_debug_delta_routes(self._h, rs, out))
+        return dict(zip(("one", "two", "four", "eight", "multi_block", "multi_block_wlist", "windows_cut", "last_records", "last_windows", "min_block"),
+                        (int(x) for x in out)))
+
+    def debug_delta_numbering(self, rs):
+        """(reads, spill): for delta index d the read of its pair and its spill index, -1 at the fixed stride (development build)."""
+        n = self._check(_lib.gaml_hip_debug_delta_numbering(self._h, rs, None, None, 0))
+        reads, spill = np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.int32)
+        self._check(_lib.gaml_hip_debug_delta_numbering(self._h, rs, reads.ctypes.data, spill.ctypes.data, n))
+        return reads[:n], spill[:n]
 
     def debug_block_partials(self, rs, set_index=0):
         sums, zeros, lay = np.zeros(8192, np.float64), np.zeros(8192, np.int32), np.zeros(8, np.int32)

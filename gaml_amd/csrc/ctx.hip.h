@@ -222,6 +222,10 @@ struct TableDev {
   // what the host knows of it once the build is through
   int64_t class_count[4] = {0, 0, 0, 0}, n0a = 0, extras[2] = {0, 0}, dropped[2] = {0, 0};
   bool keep_dominated = false;   // knob 16 when it was built
+#ifdef GAML_HIP_DEV
+  std::vector<int32_t> held[2];  // per mate: the windows whose records the tables and their delta lists took in, in that order (gaml_hip_debug_delta_check)
+  size_t held_built[2] = {0, 0}; // ... of which the first so many came with the build, the rest through the delta lists
+#endif
   std::vector<int32_t> read_of_slot_host;  // fetched on demand (gaml_hip_read_probs)
   bool ros_valid = false;
   void release() {
@@ -315,6 +319,10 @@ struct PairedSet {
   bool spill_may_grow = false;        // activations since the counts were last read back
   int dl_seq = 0;                     // sequence number of the last maintenance launch (h_dstate[kDsSeq] == dl_seq: the counts are current)
   int64_t full_rebuilds = 0, delta_updates = 0;
+  // which launches paired_delta_apply chose so far (gaml_hip_debug_delta_routes): one-block <1>, <2>, <4>, <8>, multi-block,
+  // multi-block with the window list in device memory, windows cut across launches, records / windows of the last apply,
+  // the smallest <1> block used (0: none yet)
+  int64_t dl_routes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int quiet_calls = 0;       // evaluations since the last window activation
   int64_t delta_left_out = 0, delta_left_out_base = 0;  // records of later windows that never reached the delta lists (always overwritten); the device counts them per list generation
   bool compact_requested = false;  // gaml_hip_compact_tables: fold the delta lists into the tables at the next evaluation
@@ -493,7 +501,7 @@ struct gaml_hip_ctx {
   double aln_stage_us[5] = {0, 0, 0, 0, 0};  // window strings + upload, spans + candidates, extension, D2H of hits, sort + finalize
   int64_t aln_batches = 0;
   int64_t aln_routes[4] = {0, 0, 0, 0};  // ALN_ROUTE: development builds only
-  int knobs[24] = {0};  // tuning experiments and A/B switches (gaml_hip_debug.h), development builds only: read through KNOB()
+  int knobs[25] = {0};  // tuning experiments and A/B switches (gaml_hip_debug.h), development builds only: read through KNOB()
   bool direct_write = false;  // large-BAR device: the host writes per-call tables straight into device memory (Arena)
   int32_t peers = 1;  // contexts (incl. this one) that hold reads of the same read sets: >1 => window maxima must be exchanged
   std::string err;

@@ -106,7 +106,7 @@ int gaml_hip_debug_timeline(gaml_hip_ctx* c, int rs, unsigned long long* out, in
 }
 
 int gaml_hip_debug_set_knob(gaml_hip_ctx* c, int knob, int value) {
-  if (!c || knob < 0 || knob >= 24) return GAML_HIP_EINVAL;
+  if (!c || knob < 0 || knob >= 25) return GAML_HIP_EINVAL;
   if (c->multi) { for (int k = 0; k < gaml::multi_num_shards(c->multi); k++) gaml::multi_shard(c->multi, k)->knobs[knob] = value; return GAML_HIP_OK; }
   c->knobs[knob] = value;
   return GAML_HIP_OK;
@@ -404,4 +404,240 @@ int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* c, int rs, int64_t* out, in
   const std::vector<int64_t>& b = c->paireds[c->handles[rs].idx]->batch_bad;
   for (size_t k = 0; k < b.size() && k < (size_t)cap; k++) out[k] = b[k];
   return (int32_t)b.size();
+}
+
+// The LIVE record tables plus the live delta store (delta_dev.hip.h) against the host restatement, read by read. Looks and
+// changes nothing: no rebuild started or finished, no tables prepared (gaml_hip_debug_tables_check does all three) -- it
+// waits for the stream and copies back. The reference: build_pair_tables on a copy of the device pool over the windows the
+// live tables and their lists took in (TableDev::held: the build's windows, then every window paired_delta_apply was
+// given), which yields every read's records per mate in (window id, position) order without the always-overwritten
+// junction records (knob 16 as the tables were built). While a rebuild runs beside the evaluations this covers the live
+// tables and lists only. out12 = {pairs on the lists, of those from the compact class's static part / its other part /
+// the <= 2-record class / <= 4 / more, pairs at the fixed stride with lists of up to 2 / of 3 to 4 records, long lists
+// (spill area), entries compared, mismatches, records of later windows left out (the device's count)}.
+int gaml_hip_debug_delta_check(gaml_hip_ctx* c, int rs, int64_t* out12) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1 || !out12) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  if (c->device < 0) return fail(c, GAML_HIP_ENODEVICE, "host-only context");
+  PairedSet& s = *c->paireds[c->handles[rs].idx];
+  for (int k = 0; k < 12; k++) out12[k] = 0;
+  const TableDev& T = s.tab;
+  if (!T.built || !s.delta_cap) return fail(c, GAML_HIP_ESTATE, "delta check: no live tables yet");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  static const bool trace = getenv("GAML_HIP_TRACE_HOST") != nullptr;
+  int64_t compared = 0, bad = 0;
+  int shown = 0;
+  auto miss = [&](const char* what, int64_t read, int64_t x, int64_t y) {
+    bad++;
+    if (trace && shown++ < 16) fprintf(stderr, "delta_check: %s (read %lld: %lld, %lld)\n", what, (long long)read, (long long)x, (long long)y);
+  };
+  auto expect = [&](bool ok, const char* what, int64_t read, int64_t x, int64_t y) { compared++; if (!ok) miss(what, read, x, y); };
+  // ---- the reference: the host restatement over the windows the live tables and lists hold
+  ShortMate hm[2];
+  int64_t left_out_ref = 0;
+  for (int mt = 0; mt < 2; mt++) {
+    const ShortMate& m = s.mate[mt];
+    hm[mt].n_global = m.n_global; hm[mt].lo = m.lo; hm[mt].hi = m.hi; hm[mt].lens = m.lens;
+    hm[mt].wins = m.wins;
+    hm[mt].solo_of_node = m.solo_of_node;
+    std::vector<int4> dp((size_t)s.dev[mt].pool_n);
+    if (!dp.empty()) HIP_TRY(c, hipMemcpy(dp.data(), s.dev[mt].pool.p, dp.size() * sizeof(int4), hipMemcpyDeviceToHost));
+    hm[mt].pool.resize(dp.size());
+    for (size_t k = 0; k < dp.size(); k++) hm[mt].pool[k] = gaml_aligment{dp[k].y, dp[k].z & 0xff, dp[k].w, (dp[k].z >> 8) & 1};
+    for (Window& w : hm[mt].wins) { w.active = false; w.first = w.dfirst < 0 ? 0 : w.dfirst; if (w.dfirst < 0) w.count = 0; }
+    for (int32_t wid : T.held[mt]) hm[mt].wins[(size_t)wid].active = true;
+  }
+  const bool fold = !T.keep_dominated;
+  if (fold) {
+    std::vector<uint8_t> keep;
+    for (int mt = 0; mt < 2; mt++)
+      for (size_t k = T.held_built[mt]; k < T.held[mt].size(); k++) {
+        const int32_t wid = T.held[mt][k];
+        left_out_ref += hm[mt].wins[(size_t)wid].count - undominated_records(hm[mt], wid, keep);
+      }
+  }
+  PairTables pt;
+  build_pair_tables(hm[0], hm[1], pt, fold, 0);
+  // ---- the device side
+  const int64_t n = s.mate[0].n_local();
+  const int64_t n0 = T.class_count[0], n01 = n0 + T.class_count[1], n_main = n01 + T.class_count[2], n16 = n - n0;
+  int dst[kDsInts];
+  HIP_TRY(c, hipMemcpy(dst, s.dstate.p, sizeof(dst), hipMemcpyDeviceToHost));
+  const int* hst = (const int*)s.h_dstate.p;
+  if (hst[kDsSeq] == s.dl_seq) { for (int k = 0; k < kDsInts; k++) expect(dst[k] == hst[k], "a device counter differs from its pinned copy", -1, dst[k], hst[k]); }
+  else expect(false, "the pinned counters are not those of the last maintenance launch", -1, hst[kDsSeq], s.dl_seq);
+  const int64_t nd = dst[kDsDirty], ns = dst[kDsSpill], top[2] = {dst[kDsTop0], dst[kDsTop1]};
+  expect(nd >= 0 && nd <= (int64_t)s.delta_cap && ns >= 0 && ns <= (int64_t)s.cap_spill && top[0] >= 0 && top[0] <= (int64_t)s.cap_sprec && top[1] >= 0 && top[1] <= (int64_t)s.cap_sprec,
+         "the store's counters exceed its capacity", -1, nd, ns);
+  if (bad) { out12[9] = compared; out12[10] = bad; return fail(c, GAML_HIP_ESTATE, "delta lists: the store's counters are inconsistent"); }
+  expect(dst[6] == left_out_ref, "records left out: the device's count differs from the reference's", -1, dst[6], left_out_ref);
+  {
+    const volatile int* h = hst;
+    int64_t host_left = s.delta_left_out;
+    if (h[kDsSeq] == s.dl_seq) host_left = s.delta_left_out_base + h[6];  // (what paired_refresh_counts would make of it)
+    expect(host_left - s.delta_left_out_base == left_out_ref, "delta_records_left_out differs from the reference's", -1, host_left - s.delta_left_out_base, left_out_ref);
+  }
+  std::vector<int32_t> slot_of_read((size_t)n), dirty_of_slot((size_t)n), dl_slot((size_t)nd), dl_spill((size_t)nd), sp_slot((size_t)ns);
+  std::vector<unsigned long long> rec8[2];
+  std::vector<int4> first[2], extra[2], inl0, dl_rec[2], sp_rec[2];
+  std::vector<int2> sp_rng[2];
+  auto get = [&](const DevBuf& d, void* dstp, size_t bytes) -> int {
+    if (bytes == 0) return 0;
+    if (!d.p || d.cap < bytes) return fail(c, GAML_HIP_ESTATE, "delta check: a device buffer is smaller than the counters say");
+    HIP_TRY(c, hipMemcpy(dstp, d.p, bytes, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (int e = get(T.slot_of_read, slot_of_read.data(), (size_t)n * 4)) return e;
+  if (int e = get(T.dirty_of_slot, dirty_of_slot.data(), (size_t)n * 4)) return e;
+  if (int e = get(s.dl_slot, dl_slot.data(), (size_t)nd * 4)) return e;
+  if (int e = get(s.dl_spill, dl_spill.data(), (size_t)nd * 4)) return e;
+  if (int e = get(s.sp_slot, sp_slot.data(), (size_t)ns * 4)) return e;
+  inl0.resize((size_t)(2 * T.class_count[1] + 4 * T.class_count[2]));
+  if (int e = get(T.inl[0], inl0.data(), inl0.size() * sizeof(int4))) return e;
+  for (int mt = 0; mt < 2; mt++) {
+    rec8[mt].resize((size_t)n0); first[mt].resize((size_t)n16); extra[mt].resize((size_t)T.extras[mt]);
+    dl_rec[mt].resize((size_t)nd * 4); sp_rec[mt].resize((size_t)top[mt]); sp_rng[mt].resize((size_t)ns);
+    if (int e = get(T.rec8[mt], rec8[mt].data(), (size_t)n0 * 8)) return e;
+    if (int e = get(T.first[mt], first[mt].data(), (size_t)n16 * sizeof(int4))) return e;
+    if (int e = get(T.extra[mt], extra[mt].data(), extra[mt].size() * sizeof(int4))) return e;
+    if (int e = get(s.dl_rec[mt], dl_rec[mt].data(), dl_rec[mt].size() * sizeof(int4))) return e;
+    if (int e = get(s.sp_rec[mt], sp_rec[mt].data(), sp_rec[mt].size() * sizeof(int4))) return e;
+    if (int e = get(s.sp_rng[mt], sp_rng[mt].data(), (size_t)ns * sizeof(int2))) return e;
+  }
+  std::vector<int32_t> d_seen((size_t)nd, 0), sp_seen((size_t)ns, 0);
+  std::vector<std::pair<int64_t, int64_t>> used[2];  // spill ranges in use
+  int64_t on_lists = 0, long_lists = 0;
+  std::vector<RecQuad> ref;
+  auto same = [](const int4& v, const RecQuad& r) { return v.x == r.wid && v.y == r.pos && v.z == r.flags; };
+  for (int64_t read = 0; read < n; read++) {
+    const int32_t sl = slot_of_read[(size_t)read];
+    if (sl < 0 || sl >= n) { expect(false, "slot_of_read out of range", read, sl, n); continue; }
+    const int32_t d = dirty_of_slot[(size_t)sl];
+    const int32_t l12 = (int32_t)((uint32_t)s.mate[0].lens[(size_t)read] | ((uint32_t)s.mate[1].lens[(size_t)read] << 16));
+    if (d < 0) {  // a clean pair: the tables' own lists are complete
+      for (int mt = 0; mt < 2; mt++) {
+        ref.clear();
+        paired_base_records(pt, pt.slot_of_read[(size_t)read], mt, ref);
+        if (sl < n0) {
+          const unsigned long long r = rec8[mt][(size_t)sl];
+          if (r == kDirty8) { expect(false, "a pair carries the lists' mark without a delta index", read, sl, mt); continue; }
+          const int4 v = make_int4((int)(r & 0xffffff), (int)((r >> 24) & 0xfffffff), (int)((r >> 52) & 63) | ((int)((r >> 58) & 1) << 8), 0);
+          expect(r == kNoRec8 ? ref.empty() : (ref.size() == 1 && same(make_int4(v.x, v.y, v.z & 0x1ff, 0), ref[0])), "a clean compact pair's record differs (a later record missing from the lists?)", read, sl, (int64_t)ref.size());
+        } else {
+          const int4 f = first[mt][(size_t)(sl - n0)];
+          if (f.x == kDirtyWid) { expect(false, "a pair carries the lists' mark without a delta index", read, sl, mt); continue; }
+          const int64_t cnt = f.x < 0 ? 0 : 1 + (int64_t)((unsigned)f.z >> 9);
+          expect(cnt == (int64_t)ref.size(), "a clean pair's list length differs (a later record missing from the lists?)", read, cnt, (int64_t)ref.size());
+          if (cnt != (int64_t)ref.size()) continue;
+          for (int64_t k = 0; k < cnt; k++) {
+            int4 v = k == 0 ? f : (f.w + k - 1 < (int64_t)extra[mt].size() ? extra[mt][(size_t)(f.w + k - 1)] : make_int4(-9, 0, 0, 0));
+            v.z &= 0x1ff;
+            expect(same(v, ref[(size_t)k]), "a clean pair's record differs", read, k, mt);
+          }
+        }
+      }
+      continue;
+    }
+    // a pair on the delta lists
+    on_lists++;
+    if (d >= nd) { expect(false, "delta index beyond the store's count", read, d, nd); continue; }
+    d_seen[(size_t)d]++;
+    expect(dl_slot[(size_t)d] == sl, "dl_slot is not the pair's slot", read, dl_slot[(size_t)d], sl);
+    out12[1 + (sl < T.n0a ? 0 : sl < n0 ? 1 : sl < n01 ? 2 : sl < n_main ? 3 : 4)]++;
+    // the tables' mark, where the pair's class keeps it
+    if (sl < n0) expect(rec8[0][(size_t)sl] == kDirty8, "compact pair without the lists' mark (rec8)", read, sl, 0);
+    else {
+      if (sl < n01) expect(inl0[(size_t)2 * (sl - n0)].x == kDirtyWid, "<= 2-record pair without the lists' mark (inline copy)", read, sl, 0);
+      else if (sl < n_main) expect(inl0[(size_t)2 * (n01 - n0) + (size_t)4 * (sl - n01)].x == kDirtyWid, "<= 4-record pair without the lists' mark (inline copy)", read, sl, 0);
+      expect(first[0][(size_t)(sl - n0)].x == kDirtyWid, "pair without the lists' mark (first)", read, sl, 0);
+    }
+    const int32_t sp = dl_spill[(size_t)d];
+    const int4* st4[2] = {&dl_rec[0][(size_t)4 * d], &dl_rec[1][(size_t)4 * d]};
+    size_t len[2];
+    for (int mt = 0; mt < 2; mt++) { ref.clear(); paired_base_records(pt, pt.slot_of_read[(size_t)read], mt, ref); len[mt] = ref.size(); }
+    if (sp < 0) {  // both lists at the fixed stride
+      const int hw = st4[1][0].w;
+      expect(st4[0][0].w == l12, "head word of mate 1 is not L1 | L2 << 16", read, st4[0][0].w, l12);
+      expect(hw == (int)(len[0] | (len[1] << 8)), "head word of mate 2 does not hold the two list lengths", read, hw, (int64_t)(len[0] | (len[1] << 8)));
+      expect(len[0] <= 4 && len[1] <= 4, "a list of more than 4 records at the fixed stride", read, (int64_t)len[0], (int64_t)len[1]);
+      out12[std::max(len[0], len[1]) <= 2 ? 6 : 7]++;
+      for (int mt = 0; mt < 2; mt++) {
+        ref.clear();
+        paired_base_records(pt, pt.slot_of_read[(size_t)read], mt, ref);
+        for (int k = 0; k < 4; k++) {
+          const int4 v = st4[mt][k];
+          if (k < (int)ref.size()) expect(same(v, ref[(size_t)k]) && (k == 0 || v.w == 0), "a record at the fixed stride differs", read, k, mt);
+          else expect(v.x == -1 && v.y == 0 && v.z == 0 && (k == 0 || v.w == 0), "an unused stride entry is not {-1, 0, 0, 0}", read, k, mt);
+        }
+      }
+    } else {
+      long_lists++;
+      if (sp >= ns) { expect(false, "spill index beyond the store's count", read, sp, ns); continue; }
+      sp_seen[(size_t)sp]++;
+      expect(sp_slot[(size_t)sp] == sl, "sp_slot is not the pair's slot", read, sp_slot[(size_t)sp], sl);
+      expect(len[0] > 4 || len[1] > 4, "a pair in the spill area whose lists fit the fixed stride", read, (int64_t)len[0], (int64_t)len[1]);
+      for (int mt = 0; mt < 2; mt++) {
+        ref.clear();
+        paired_base_records(pt, pt.slot_of_read[(size_t)read], mt, ref);
+        const int2 g = sp_rng[mt][(size_t)sp];
+        expect(g.y == (int)ref.size(), "a spill range's length differs", read, g.y, (int64_t)ref.size());
+        const bool in = g.x >= 0 && g.y >= 0 && (int64_t)g.x + g.y <= top[mt];
+        expect(in, "a spill range reaches beyond the area's top", read, g.x, g.y);
+        if (in && g.y > 0) used[mt].emplace_back(g.x, g.y);
+        if (in && g.y == (int)ref.size())
+          for (int k = 0; k < g.y; k++) { const int4 v = sp_rec[mt][(size_t)g.x + k]; expect(same(v, ref[(size_t)k]) && v.w == 0, "a record in the spill area differs", read, k, mt); }
+        for (int k = 0; k < 4; k++) {  // the stride entries of a spilled pair: empty, the read lengths in the first spare word, no stale counts
+          const int4 v = st4[mt][k];
+          expect(v.x == -1 && v.y == 0 && v.z == 0 && v.w == (k == 0 && mt == 0 ? l12 : 0), "a spilled pair's stride entry is not empty (stale head word?)", read, k, mt);
+        }
+      }
+    }
+  }
+  expect(on_lists == nd, "pairs with a delta index differ from the store's count", -1, on_lists, nd);
+  for (int64_t d = 0; d < nd; d++) if (d_seen[(size_t)d] != 1) expect(false, "a delta index is used by no pair or by several", -1, d, d_seen[(size_t)d]);
+  expect(long_lists == ns, "pairs with a spill index differ from the store's count", -1, long_lists, ns);
+  for (int64_t q = 0; q < ns; q++) if (sp_seen[(size_t)q] != 1) expect(false, "a spill index is used by no pair or by several", -1, q, sp_seen[(size_t)q]);
+  for (int mt = 0; mt < 2; mt++) {
+    std::sort(used[mt].begin(), used[mt].end());
+    for (size_t k = 1; k < used[mt].size(); k++) expect(used[mt][k - 1].first + used[mt][k - 1].second <= used[mt][k].first, "two spill ranges overlap", -1, used[mt][k - 1].first, used[mt][k].first);
+  }
+  out12[0] = on_lists; out12[8] = long_lists; out12[9] = compared; out12[10] = bad; out12[11] = dst[6];
+  return bad ? fail(c, GAML_HIP_ESTATE, "delta lists: the live tables and lists differ from the host restatement") : GAML_HIP_OK;
+}
+
+// Which launches the delta maintenance chose so far (paired_delta_apply): out10 = {one-block launches of delta_apply_kernel
+// <1>, <2>, <4>, <8>, multi-block launches, of those with the window list in device memory, windows cut across launches,
+// records and windows of the last apply, the smallest <1> block used (0: none)}.
+int gaml_hip_debug_delta_routes(gaml_hip_ctx* c, int rs, int64_t* out10) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1 || !out10) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const PairedSet& s = *c->paireds[c->handles[rs].idx];
+  for (int k = 0; k < 10; k++) out10[k] = s.dl_routes[k];
+  return GAML_HIP_OK;
+}
+
+// The numbering of the live delta lists: for delta index d the READ of its pair and its spill index (-1: fixed stride).
+// Returns the number of pairs on the lists; at most `cap` are written.
+int32_t gaml_hip_debug_delta_numbering(gaml_hip_ctx* c, int rs, int32_t* reads, int32_t* spill, int32_t cap) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1 || cap < 0 || (cap > 0 && (!reads || !spill))) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  if (c->device < 0) return fail(c, GAML_HIP_ENODEVICE, "host-only context");
+  PairedSet& s = *c->paireds[c->handles[rs].idx];
+  if (!s.tab.built || !s.delta_cap) return 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int dst[kDsInts];
+  HIP_TRY(c, hipMemcpy(dst, s.dstate.p, sizeof(dst), hipMemcpyDeviceToHost));
+  const int nd = dst[kDsDirty];
+  if (nd < 0 || (size_t)nd > s.delta_cap) return fail(c, GAML_HIP_ESTATE, "delta lists: the store's count exceeds its capacity");
+  const int k = std::min<int>(nd, cap);
+  if (k == 0) return nd;
+  const int64_t n = s.mate[0].n_local();
+  std::vector<int32_t> slot((size_t)k), ros((size_t)n);
+  HIP_TRY(c, hipMemcpy(slot.data(), s.dl_slot.p, (size_t)k * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(spill, s.dl_spill.p, (size_t)k * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(ros.data(), s.tab.read_of_slot.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (int d = 0; d < k; d++) reads[d] = slot[(size_t)d] >= 0 && slot[(size_t)d] < n ? ros[(size_t)slot[(size_t)d]] : -1;
+  return nd;
 }

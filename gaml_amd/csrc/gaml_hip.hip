@@ -1163,6 +1163,17 @@ static int wait_host_partials(gaml_hip_ctx* c, bool* spun) {
   return 0;
 }
 
+// The device is through with everything enqueued: the delta lists' exact counts are in pinned memory. A maintenance launch
+// that found the store full changed nothing and raised a flag -- the values scored after it lack the records of the windows
+// it was to take in, so every route that hands values to the caller (single calls, batches, gap profiles) refuses them here.
+static int paired_counts_after_wait(gaml_hip_ctx* c) {
+  for (auto& ps : c->paireds) {
+    paired_refresh_counts(*ps);
+    if (paired_delta_overflowed(*ps)) return fail(c, GAML_HIP_ESTATE, "delta store overflow (spill area); call gaml_hip_compact_tables and evaluate again");
+  }
+  return 0;
+}
+
 static int fetch_partials(gaml_hip_ctx* c, double* partials_out) {
   bool spun = false;
   if (int e = wait_host_partials(c, &spun)) return e;
@@ -1183,10 +1194,7 @@ static int fetch_partials(gaml_hip_ctx* c, double* partials_out) {
   memcpy(partials_out, c->packed_host.p, c->handles.size() * 4 * sizeof(double));
   // the device is through with this evaluation: the delta lists' exact counts are in pinned memory (written by the kernels
   // that maintain them, in stream order before the scoring launch)
-  for (auto& ps : c->paireds) {
-    paired_refresh_counts(*ps);
-    if (paired_delta_overflowed(*ps)) return fail(c, GAML_HIP_ESTATE, "delta store overflow (spill area); call gaml_hip_compact_tables and evaluate again");
-  }
+  if (int e = paired_counts_after_wait(c)) return e;
   c->t_kernel_us = 0;
   if (!spun) { if (int e2 = collect_events(c)) return e2; }  // after a spin the events are collected lazily (gaml_hip_kernel_stats)
   // bookkeeping for gaml_hip_bad_bases
@@ -1292,6 +1300,7 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* c, int32_t n_sets, const int32_t* pat
   }
   HIP_TRY(c, hipMemcpyAsync(c->batch_host.p, c->batch_dev.p, doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int e = paired_counts_after_wait(c)) return e;  // (the sequential path: stream-ordered evaluations, nobody has looked at the flag yet)
   const double* res = (const double*)c->batch_host.p;
   {
     auto order = scoring_order(c);

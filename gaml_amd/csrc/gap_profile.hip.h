@@ -208,7 +208,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     bool spun = false;
     if (int e = wait_host_partials(c, &spun)) return e;
     if (!spun) { if (int e2 = collect_events(c)) return e2; }
-    for (auto& ps : c->paireds) paired_refresh_counts(*ps);
+    if (int e = paired_counts_after_wait(c)) return e;
     for (int k = 0; k < n; k++) {
       for (size_t i = 0; i < nps; i++) {
         PairedSet& ps = *c->paireds[i];

@@ -240,6 +240,9 @@ int paired_build_enqueue(gaml_hip_ctx* c, PairedSet& s, TableDev& T, hipStream_t
       TbWin* hw = (TbWin*)B.h_wins[mt].p;
       int k = 0;
       int64_t at = 0;
+#ifdef GAML_HIP_DEV
+      T.held[mt].clear();
+#endif
       for (size_t wid = 0; wid < m.wins.size(); wid++) {
         const Window& w = m.wins[wid];
         if (!w.active || w.count == 0) continue;
@@ -249,7 +252,13 @@ int paired_build_enqueue(gaml_hip_ctx* c, PairedSet& s, TableDev& T, hipStream_t
         dominating_window(m, w, fold, &t.dom_first, &t.dom_count);
         hw[k++] = t;
         at += w.count;
+#ifdef GAML_HIP_DEV
+        T.held[mt].push_back((int32_t)wid);
+#endif
       }
+#ifdef GAML_HIP_DEV
+      T.held_built[mt] = T.held[mt].size();
+#endif
       if (at >= ((int64_t)1 << 31)) return fail(c, GAML_HIP_EINVAL, "table build: more than 2^31 active records per mate");
       P.A[mt] = at; P.n_act[mt] = k;
       HIP_TRY(c, B.wins[mt].reserve((2 * m.wins.size() + 16384) * sizeof(TbWin)));
@@ -406,6 +415,7 @@ int paired_reserve_delta(gaml_hip_ctx* c, PairedSet& s) {
   s.delta_cap = (size_t)std::max<int64_t>(4096, np_all / 2) + 8192;
   s.cap_spill = (size_t)(65536 + np_all / 16);
   s.cap_sprec = (size_t)((2 << 20) + np_all);
+  if (KNOB(c, 24) > 0) { s.cap_spill = (size_t)KNOB(c, 24); s.cap_sprec = (size_t)16 * (size_t)KNOB(c, 24); }  // knob 24 = n: room for n long lists, 16 n records per mate (tests of the overflow path)
   HIP_TRY(c, s.dl_slot.reserve(s.delta_cap * sizeof(int32_t)));
   HIP_TRY(c, s.dl_spill.reserve(s.delta_cap * sizeof(int32_t)));
   for (int mt = 0; mt < 2; mt++) {
@@ -493,6 +503,8 @@ int paired_delta_apply(gaml_hip_ctx* c, PairedSet& s, TableDev& T, std::vector<s
         if (int e = stage_release(c, s.stage_pool, slot, st)) return e;
         a.wlist = s.dl_wlist.as<DlWin>();
       }
+      s.dl_routes[4]++;
+      if (a.wlist) s.dl_routes[5]++;
       hipLaunchKernelGGL(delta_mb_begin_kernel, dim3(1), dim3(64), 0, st, a.blk_tot);
       hipLaunchKernelGGL(delta_mb_keys_kernel, dim3((unsigned)std::min(256, (a.n_total + 255) / 256)), dim3(256), 0, st, a);
       hipLaunchKernelGGL((delta_apply_kernel<8, 1>), dim3(kDlBins), dim3(kDlThreads), 0, st, a);
@@ -507,10 +519,16 @@ int paired_delta_apply(gaml_hip_ctx* c, PairedSet& s, TableDev& T, std::vector<s
       big.clear();
       return 0;
     }
-    if (a.n_total <= kDlThreads) { int thr = 64; while (thr < a.n_total) thr <<= 1; hipLaunchKernelGGL(delta_apply_kernel<1>, dim3(1), dim3(thr), 0, st, a); }
-    else if (a.n_total <= 2 * kDlThreads) hipLaunchKernelGGL(delta_apply_kernel<2>, dim3(1), dim3(kDlThreads), 0, st, a);
-    else if (a.n_total <= 4 * kDlThreads) hipLaunchKernelGGL(delta_apply_kernel<4>, dim3(1), dim3(kDlThreads), 0, st, a);
-    else hipLaunchKernelGGL(delta_apply_kernel<8>, dim3(1), dim3(kDlThreads), 0, st, a);
+    if (a.n_total <= kDlThreads) {
+      int thr = 64;
+      while (thr < a.n_total) thr <<= 1;
+      hipLaunchKernelGGL(delta_apply_kernel<1>, dim3(1), dim3(thr), 0, st, a);
+      s.dl_routes[0]++;
+      if (s.dl_routes[9] == 0 || thr < s.dl_routes[9]) s.dl_routes[9] = thr;
+    }
+    else if (a.n_total <= 2 * kDlThreads) { hipLaunchKernelGGL(delta_apply_kernel<2>, dim3(1), dim3(kDlThreads), 0, st, a); s.dl_routes[1]++; }
+    else if (a.n_total <= 4 * kDlThreads) { hipLaunchKernelGGL(delta_apply_kernel<4>, dim3(1), dim3(kDlThreads), 0, st, a); s.dl_routes[2]++; }
+    else { hipLaunchKernelGGL(delta_apply_kernel<8>, dim3(1), dim3(kDlThreads), 0, st, a); s.dl_routes[3]++; }
     HIP_TRY(c, hipGetLastError());
 #ifdef GAML_HIP_DEV
     if (stamp) {
@@ -527,10 +545,15 @@ int paired_delta_apply(gaml_hip_ctx* c, PairedSet& s, TableDev& T, std::vector<s
     return 0;
   };
   const int max_wins = multi_block ? 16384 : kDlMaxWins;
+  s.dl_routes[7] = all_records; s.dl_routes[8] = 0;
   for (const auto& mw : wins) {
     const ShortMate& m = s.mate[mw.first];
     const Window& w = m.wins[mw.second];
     if (w.count == 0) continue;
+    s.dl_routes[8]++;
+#ifdef GAML_HIP_DEV
+    T.held[mw.first].push_back(mw.second);
+#endif
     if (w.dfirst < 0) return fail(c, GAML_HIP_ESTATE, "delta lists: an activated window's records are not in the device pool");
     int dom_first, dom_count;
     dominating_window(m, w, fold, &dom_first, &dom_count);
@@ -538,6 +561,7 @@ int paired_delta_apply(gaml_hip_ctx* c, PairedSet& s, TableDev& T, std::vector<s
     while (done < w.count) {  // (a window larger than a launch holds is cut: the lists compose)
       if (a.n_wins == max_wins || a.n_total == max_recs) { if (int e = flush()) return e; }
       const int take = std::min(w.count - done, max_recs - a.n_total);
+      if (done == 0 && take < w.count) s.dl_routes[6]++;
       const DlWin dw{mw.first, mw.second, (int)w.dfirst + done, take, dom_first, dom_count, a.n_total};
       if (a.n_wins < kDlMaxWins) a.w[a.n_wins] = dw;
       if (multi_block) big.push_back(dw);

@@ -78,7 +78,9 @@ int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int
  * part, 21 = 1: a set with a coverage penalty scores its compact class in the general form (three table loads per pair, no
  * streamed values: the route of every penalised set before the marks moved into the memo bodies), 22 = 1: delta maintenance by one-block launches only (default: multi-block
  * above 3,000 records), 23 = n > 0: the window aligner's general route starts with room for n spans and n candidates instead of
- * its estimate from the window bases (its retry loop then grows both; same records either way). Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */
+ * its estimate from the window bases (its retry loop then grows both; same records either way), 24 = n > 0: the delta store's spill area
+ * holds n long lists and 16 n records per mate (read when the store is reserved: set it before the first evaluation; tests of
+ * the overflow path). Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */
 /* Ablation 8 (knob 3 = 8) of the last evaluation of paired read set rs: 8 wall-clock stamps (10 ns units) per wave,
  * [kernel entry, tables in LDS, records in, occurrences in, memo in, stores issued, block reduced, class]. Returns the
  * number of waves copied. Tuning aid (tools/kernel_timeline.py). */
@@ -136,6 +138,25 @@ int gaml_hip_debug_aligner_routes(gaml_hip_ctx* ctx, int64_t* out4);
  * A batch over penalised sets: knob 11 = 0 the one-pass routes (tables from patches, else whole; the capture of unchanged
  * pairs is always off for such a launch, so 3 equals 0 there), 2 whole tables per set, 1 one call per path set. */
 int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* ctx, int readset, int64_t* out, int32_t cap);
+
+/* The LIVE record tables plus the live delta lists (gaml_amd/csrc/delta_dev.hip.h) of paired set `readset` against the host
+ * restatement build_pair_tables, read by read, over the windows the tables and their lists took in. Inspects and changes
+ * nothing: starts no rebuild, finishes none, prepares no tables (gaml_hip_debug_tables_check does all three); while a rebuild
+ * runs beside the evaluations it covers the live tables and lists only. For every pair on the lists: its list (fixed stride
+ * or spill range) record for record, the head words (L1 | L2 << 16, the two list lengths), the unused stride entries, its
+ * slot and the tables' mark; for every other pair: the tables' own list is complete; the numbering 0 .. n-1, the spill
+ * ranges in use (below the area's top, disjoint), the device counters against their pinned copy, the records left out.
+ * out12 = {pairs on the lists, of those from the compact class's static part, its other part, the <= 2-record class, <= 4,
+ * more, pairs at the fixed stride with lists of up to 2 records, of 3 to 4, long lists, entries compared, mismatches, records
+ * of later windows left out}; GAML_HIP_ESTATE on a mismatch (GAML_HIP_TRACE_HOST=1 prints the first sixteen). */
+int gaml_hip_debug_delta_check(gaml_hip_ctx* ctx, int readset, int64_t* out12);
+/* Which launches the delta maintenance of paired set `readset` chose so far: out10 = {one-block launches with 1, 2, 4, 8
+ * records per thread, multi-block launches, of those with the window list in device memory, windows cut across launches,
+ * records and windows of the last maintenance call, the smallest block of a one-record-per-thread launch (0: none)}. */
+int gaml_hip_debug_delta_routes(gaml_hip_ctx* ctx, int readset, int64_t* out10);
+/* The live lists' numbering: reads[d] = the read of the pair with delta index d, spill[d] = its spill index (-1: fixed
+ * stride). Returns the number of pairs on the lists; at most `cap` are written. */
+int32_t gaml_hip_debug_delta_numbering(gaml_hip_ctx* ctx, int readset, int32_t* reads, int32_t* spill, int32_t cap);
 
 #ifdef __cplusplus
 }

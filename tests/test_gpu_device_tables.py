@@ -1,6 +1,8 @@
 """The record tables are built and maintained ON THE DEVICE (table_build.hip.h, delta_dev.hip.h): the read-major join the
 reference does per call through hash maps (graph.cc:535-598) over its window cache (graph.cc:911-922). The device build
-is compared with the host restatement entry by entry; the delta lists against tables rebuilt from scratch and the oracle."""
+of fresh tables is compared with the host restatement entry by entry, and two builds of one state with each other. The delta
+lists themselves -- every maintenance launch, the lists read by read, tables rebuilt from scratch, the oracle -- are compared
+in tests/test_gpu_delta_lists.py."""
 import numpy as np
 import pytest
 
