@@ -7,6 +7,7 @@ raises GamlHipError(ENODEVICE).
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import importlib.util
 import os
 import sys
@@ -54,6 +55,80 @@ def paired_cfg(insert_mean, insert_std, penalty_constant=0.0, penalty_step=50.0,
     """Defaults of the reference's config reader (gaml.cc:851-862); step = insert_mean - penalty_step."""
     return PairedCfg(penalty_constant, insert_mean - penalty_step, insert_mean, insert_std, min_prob_per_base,
                      min_prob_start, weight, mismatch_prob)
+
+
+
+class Knob(enum.IntEnum):
+    """The development build's A/B switches and tuning knobs: enum gaml_hip_knob of include/gaml_hip_debug.h, which says what
+    each one does (tests/test_abi.py holds the two lists together). Every knob is 0 by default."""
+    GRID_CAP_COMPACT = 0
+    SCORE_LDS_BYTES = 1
+    FINISH_MODE = 2
+    TIMELINE = 3
+    NO_MEMO = 4
+    ALIGNER_ROUTE = 5
+    DELTA_POLICY = 6
+    NO_SPIN = 7
+    UPLOAD_ROUTE = 8
+    ALIGNER_TIMED = 9
+    GRID_CAP_CLASS1 = 10
+    BATCH_ROUTE = 11
+    PLAN_WHOLE_SET = 12
+    NO_RESIDENT_TABLES = 13
+    REBUILD_ON_CALLER = 14
+    NO_RETIRE = 15
+    KEEP_DOMINATED = 16
+    NO_OCC_DEVICE = 17
+    GAP_FALLBACK = 18
+    NO_STATIC_INDEX = 19
+    GRID_CAP_COMPACT_REST = 20
+    NO_COV_INSTANCE = 21
+    DELTA_ONE_BLOCK = 22
+    ALIGNER_FIRST_CAP = 23
+    DELTA_SPILL_CAP = 24
+    TAKE_OVER_AFTER = 25
+    REBUILD_DIVISOR = 26
+
+
+KNOB_COUNT = len(Knob)
+
+
+# the values of the knobs that choose between routes (the enums of the same names in gaml_hip_debug.h); 0 is every one's default
+class FinishMode(enum.IntEnum):
+    LAST_BLOCK = 1
+    KERNEL = 2
+
+
+class AlignerRoute(enum.IntEnum):
+    HOST = 1
+    HOST_SORT = 2
+    GENERAL = 3
+    PER_MATE = 4
+    INPUT_BLOCK = 5
+    HOST_FILING = 6
+
+
+class DeltaPolicy(enum.IntEnum):
+    NO_LISTS = 1
+    NO_QUIET_REBUILD = 2
+
+
+class UploadRoute(enum.IntEnum):
+    MEMCPY = 1
+    COPY_KERNEL = 2
+
+
+class BatchRoute(enum.IntEnum):
+    SEQUENTIAL = 1
+    FULL_TABLES = 2
+    NO_CAPTURE = 3
+
+
+def parse_knob(text):
+    """'NAME=V' or 'N=V' (a probe's command line) -> (knob, value); a number passes through as it is, for a library built
+    from an older tree."""
+    k, v = text.split("=")
+    return (int(k) if k.strip().lstrip("-").isdigit() else Knob[k.strip().upper()]), int(v)
 
 
 class BatchPaths:
@@ -816,13 +891,14 @@ class Context:
         return out
 
     def debug_timeline(self, rs: int, cap_waves: int = 1 << 16) -> np.ndarray:
-        """[waves, 8] wall-clock stamps (10 ns units) of the last evaluation run with knob 3 = 8."""
+        """[waves, 8] wall-clock stamps (10 ns units) of the last evaluation run with Knob.TIMELINE = 8."""
         out = np.zeros((cap_waves, 8), np.uint64)
         n = self._check(_lib.gaml_hip_debug_timeline(self._h, rs, out.ctypes.data, cap_waves))
         return out[:n]
 
     def debug_set_knob(self, knob, value):
-        self._check(_lib.gaml_hip_debug_set_knob(self._h, knob, value))
+        """knob: a Knob, or its number (what a library built from an older tree understands)."""
+        self._check(_lib.gaml_hip_debug_set_knob(self._h, int(knob), int(value)))
 
     def debug_fold_check(self, rs):
         """Host-only: record tables with / without the always-overwritten records, compared pair by pair."""

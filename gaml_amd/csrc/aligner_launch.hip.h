@@ -85,7 +85,7 @@ int aln_small_reserve(gaml_hip_ctx* c, AlignSmall& S) {
   HIP_TRY(c, S.wcopy.reserve(((size_t)1 << 18) + 64));  // a batch's window strings in ordinary device memory (span_cands_kernel writes, extend_pair2_kernel reads)
   if (!S.out_host.p) { HIP_TRY(c, S.out_host.reserve(64 + 64 + (size_t)kFastCands * sizeof(AlnHit))); memset(S.out_host.p, 0, 128); }
   if (!S.in_dev) {
-    const bool direct = c->direct_write && KNOB(c, 8) == 0;
+    const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
     const size_t want = (size_t)1 << 18;
     if (direct) HIP_TRY(c, hipExtMallocWithFlags(&S.in_dev, want, hipDeviceMallocFinegrained));
     else { HIP_TRY(c, hipMalloc(&S.in_dev, want)); HIP_TRY(c, S.in_host.reserve(want)); }
@@ -95,7 +95,7 @@ int aln_small_reserve(gaml_hip_ctx* c, AlignSmall& S) {
 }
 
 bool aln_gpu_capable(const gaml_hip_ctx* c, const ShortMate& m) {
-  return !(c->device < 0 || KNOB(c, 5) == 1 || m.index_read_len < 16 || m.max_len > kAlnWideRead || m.n_local() == 0 || m.bucket_hash.empty());
+  return !(c->device < 0 || KNOB(c, ALIGNER_ROUTE) == GAML_HIP_ALIGNER_HOST || m.index_read_len < 16 || m.max_len > kAlnWideRead || m.n_local() == 0 || m.bucket_hash.empty());
 }
 
 // which instantiation this mate's own launches take
@@ -125,7 +125,7 @@ int aln_small_enqueue(gaml_hip_ctx* c, const ShortMate& m, AlignDev& d, AlignSma
   const size_t in_bytes = align16(nw * sizeof(AlnWindow)) + align16((nw + 1) * sizeof(int32_t)) + align16(job.wstr.size() + 16);
   if (nw == 0 || nw > 4096 || in_bytes > ((size_t)1 << 20) || job.blk[(size_t)nw] == 0) return 1;
   // input block: [windows][code-buffer offsets][window strings]
-  const bool direct = c->direct_write && KNOB(c, 8) == 0;
+  const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
   if (in_bytes > S.in_cap || S.in_direct != direct) {
     HIP_TRY(c, hipStreamSynchronize(st));
     if (S.in_dev) { HIP_TRY(c, hipFree(S.in_dev)); S.in_dev = nullptr; }
@@ -334,7 +334,7 @@ void aln_file_hits(ShortMate& m, int nw, std::vector<AlnHit>& hits, bool device_
 // ---------------------------------------------------------------------------------------------------------
 int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
   ShortMate* mm[2] = {&ps.mate[0], &ps.mate[1]};
-  if (KNOB(c, 5) == 3 || KNOB(c, 5) == 4) return 1;  // knob 5 = 3: general route, 4: one small pipeline per mate (A/B, tests)
+  if (KNOB(c, ALIGNER_ROUTE) == GAML_HIP_ALIGNER_GENERAL || KNOB(c, ALIGNER_ROUTE) == GAML_HIP_ALIGNER_PER_MATE) return 1;  // (A/B, tests)
   for (int mt = 0; mt < 2; mt++) if (mm[mt]->pending.empty() || !aln_gpu_capable(c, *mm[mt])) return 1;
   for (int mt = 0; mt < 2; mt++) if (ps.dev[mt].aln.uploaded && ps.dev[mt].aln.hbits == 0) return 1;  // no key table (aln_upload_index)
   const double t0 = now_us();
@@ -368,11 +368,11 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
   const size_t in_bytes = align16(nw * sizeof(AlnWindow)) + align16((nw + 1) * sizeof(int32_t)) + align16(job.wstr.size() + 16);
   if (nw > 4096 || in_bytes > ((size_t)1 << 18) || job.blk[(size_t)nw] == 0) return 1;
   if (int e = aln_small_reserve(c, S)) return e;
-  const bool direct = c->direct_write && KNOB(c, 8) == 0;
+  const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
   if (in_bytes > S.in_cap || S.in_direct != direct) return 1;  // (the per-mate route sizes its own input block)
   // a handful of windows and their strings travel with the launches themselves (AlnWinArgs, AlnStrArgs); otherwise
   // through the input block: [windows][code-buffer offsets][window strings]
-  const bool in_args = nw <= kAlnArgWins && job.wstr.size() <= (size_t)kAlnArgStr && KNOB(c, 5) != 5;  // knob 5 = 5: always the input block (tests)
+  const bool in_args = nw <= kAlnArgWins && job.wstr.size() <= (size_t)kAlnArgStr && KNOB(c, ALIGNER_ROUTE) != GAML_HIP_ALIGNER_INPUT_BLOCK;  // INPUT_BLOCK: always the input block (tests)
   const size_t off_blk = align16(nw * sizeof(AlnWindow)), off_str = off_blk + align16((nw + 1) * sizeof(int32_t));
   if (!in_args) {
     char* wp = (char*)S.in_dev;
@@ -453,8 +453,8 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
   char* oh = (char*)S.out_host.dev;
   // The hits are filed on the device (aligner_file.hip.h): ordered, de-duplicated and appended to the mates' record pools by
   // one more small dispatch; the host gets the windows' headers back. Not when the batch has more windows than the filing
-  // kernel's argument block names (knob 5 = 6: never -- the host files, A/B and tests).
-  const bool file_dev = nw <= kFileMaxWins && KNOB(c, 5) != 6 && !timed;
+  // kernel's argument block names (HOST_FILING: never -- the host files, A/B and tests).
+  const bool file_dev = nw <= kFileMaxWins && KNOB(c, ALIGNER_ROUTE) != GAML_HIP_ALIGNER_HOST_FILING && !timed;
   if (file_dev) {
     for (int mt = 0; mt < 2; mt++) if (int e = pool_reserve(c, ps, mt, ps.dev[mt].pool_n + kFileMaxHits)) return e;
     if (int e = pool_mirror(c, ps, st)) return e;  // (windows the host filed earlier come first in the pools)
@@ -594,7 +594,7 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
   unsigned nc = 0;
   std::vector<AlnHit> hits;
   double t1 = now_us(), t2 = t1, t3 = t1;
-  if (small && KNOB(c, 5) != 3) {  // knob 5 = 3: always the general route (tests compare the two)
+  if (small && KNOB(c, ALIGNER_ROUTE) != GAML_HIP_ALIGNER_GENERAL) {  // (tests compare the two)
     int rc = job.enqueued ? 0 : aln_small_enqueue(c, m, d, *small, job, c->stream);
     if (rc == 0) rc = aln_small_collect(c, *small, job, hits, &nc);
     if (rc < 0) return rc;
@@ -618,7 +618,7 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
   t1 = now_us();
   size_t cap_spans = std::max<size_t>(1 << 16, wstr.size());        // a span per window base and strand at most ~2x
   size_t cap_cands = std::max<size_t>(1 << 18, 8 * wstr.size());
-  if (KNOB(c, 23) > 0) cap_spans = cap_cands = (size_t)KNOB(c, 23);  // knob 23: first capacities (tests of the retry loop below)
+  if (KNOB(c, ALIGNER_FIRST_CAP) > 0) cap_spans = cap_cands = (size_t)KNOB(c, ALIGNER_FIRST_CAP);  // first capacities (tests of the retry loop below)
   unsigned counts[2] = {0, 0};
   for (int attempt = 0; attempt < 6; attempt++) {
     HIP_TRY(c, S.spans.reserve(cap_spans * sizeof(AlnSpan)));
@@ -650,14 +650,14 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
                        (unsigned)cap_cands, S.wstr.as<char>(), S.wins.as<AlnWindow>(), d.reads.as<char>(), d.read_off.as<int64_t>(),
                        S.hits.as<AlnHit>());
     HIP_TRY(c, hipGetLastError());
-    if (KNOB(c, 9)) {
+    if (KNOB(c, ALIGNER_TIMED)) {
       HIP_TRY(c, hipStreamSynchronize(st)); t3 = now_us();
     }
     // Large batches: order the hits on the device (window, position, read, strand, order; failed extensions
     // last) and fetch only the successful ones; the host then only walks them. Keys: read < 2^31, order < 2^24.
     int32_t longest = 0;  // (the device sort packs a span's order -- an index into its window -- into 24 bits)
     for (const AlnWindow& w : wins) longest = std::max(longest, w.len);
-    if (nc >= 100000 && KNOB(c, 5) != 2 && longest < (1 << 24)) {
+    if (nc >= 100000 && KNOB(c, ALIGNER_ROUTE) != GAML_HIP_ALIGNER_HOST_SORT && longest < (1 << 24)) {
       const size_t n = nc;
       HIP_TRY(c, S.sort_keys.reserve(4 * n * sizeof(unsigned long long)));   // minor | major | two alternates
       HIP_TRY(c, S.sort_idx.reserve(3 * n * sizeof(unsigned)));
@@ -685,8 +685,8 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
       unsigned ok_count = 0;
       HIP_TRY(c, hipMemcpyAsync(&ok_count, n_ok, sizeof(unsigned), hipMemcpyDeviceToHost, st)); HIP_TRY(c, hipStreamSynchronize(st));
       gpu_probe(st, c->warm_buf.p, "  extension + sorts done");
-      if (KNOB(c, 9)) t3 = now_us();
-      if (ps && KNOB(c, 5) != 6 && ok_count > 0 && n < ((size_t)1 << 30)) {
+      if (KNOB(c, ALIGNER_TIMED)) t3 = now_us();
+      if (ps && KNOB(c, ALIGNER_ROUTE) != GAML_HIP_ALIGNER_HOST_FILING && ok_count > 0 && n < ((size_t)1 << 30)) {
         // filed on the device: survivors flagged, placed by a prefix sum, written into this mate's pool; the windows' headers come back
         MateDev& md = ps->dev[mt];
         if (int e = pool_mirror(c, *ps, st)) return e;  // (windows the host filed earlier come first in the pool)
@@ -749,7 +749,7 @@ int gpu_align_pending(gaml_hip_ctx* c, ShortMate& m, AlignDev& d, AlignSmall* sm
   }
   }  // general route
   const double t4 = now_us();
-  if (!KNOB(c, 9)) t3 = t4;
+  if (!KNOB(c, ALIGNER_TIMED)) t3 = t4;
   aln_file_hits(m, nw, hits, device_sorted);
   m.pending.clear();
   c->aln_windows += nw;
@@ -771,7 +771,7 @@ int align_pending_pair(gaml_hip_ctx* c, PairedSet& ps) {
   // the end of this call stalled the device's queues for 12-25 ms, see AlignScratch::stage)
   AlnJob* const job = c->aln_job;
   for (int q = 0; q < 2; q++) { job[q].prepared = false; job[q].enqueued = false; job[q].wstr.clear(); job[q].wins.clear(); job[q].blk.clear(); }
-  if (c->device >= 0 && KNOB(c, 5) != 3) {
+  if (c->device >= 0 && KNOB(c, ALIGNER_ROUTE) != GAML_HIP_ALIGNER_GENERAL) {
     for (int mt = 0; mt < 2; mt++) {
       ShortMate& m = ps.mate[mt];
       if (m.pending.empty() || !aln_gpu_capable(c, m)) continue;

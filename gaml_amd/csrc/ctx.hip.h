@@ -37,9 +37,10 @@
 
 
 // A/B switches and tuning knobs (gaml_hip_debug_set_knob) exist in development builds (-DGAML_HIP_DEV) only; the release
-// library is compiled with every one of them at its default, 0.
+// library is compiled with every one of them at its default, 0. KNOB(c, NO_MEMO) reads GAML_HIP_KNOB_NO_MEMO of enum
+// gaml_hip_knob (include/gaml_hip_debug.h: the one list of them).
 #ifdef GAML_HIP_DEV
-#define KNOB(c, i) ((c)->knobs[i])
+#define KNOB(c, i) ((c)->knobs[GAML_HIP_KNOB_##i])
 #else
 #define KNOB(c, i) 0
 #endif
@@ -221,7 +222,7 @@ struct TableDev {
   bool built = false;
   // what the host knows of it once the build is through
   int64_t class_count[4] = {0, 0, 0, 0}, n0a = 0, extras[2] = {0, 0}, dropped[2] = {0, 0};
-  bool keep_dominated = false;   // knob 16 when it was built
+  bool keep_dominated = false;   // KEEP_DOMINATED when it was built
 #ifdef GAML_HIP_DEV
   std::vector<int32_t> held[2];  // per mate: the windows whose records the tables and their delta lists took in, in that order (gaml_hip_debug_delta_check)
   size_t held_built[2] = {0, 0}; // ... of which the first so many came with the build, the rest through the delta lists
@@ -501,7 +502,7 @@ struct gaml_hip_ctx {
   double aln_stage_us[5] = {0, 0, 0, 0, 0};  // window strings + upload, spans + candidates, extension, D2H of hits, sort + finalize
   int64_t aln_batches = 0;
   int64_t aln_routes[4] = {0, 0, 0, 0};  // ALN_ROUTE: development builds only
-  int knobs[25] = {0};  // tuning experiments and A/B switches (gaml_hip_debug.h), development builds only: read through KNOB()
+  int knobs[GAML_HIP_KNOB_COUNT] = {0};  // tuning experiments and A/B switches (gaml_hip_debug.h), development builds only: read through KNOB()
   bool direct_write = false;  // large-BAR device: the host writes per-call tables straight into device memory (Arena)
   int32_t peers = 1;  // contexts (incl. this one) that hold reads of the same read sets: >1 => window maxima must be exchanged
   std::string err;

@@ -106,7 +106,7 @@ int gaml_hip_debug_timeline(gaml_hip_ctx* c, int rs, unsigned long long* out, in
 }
 
 int gaml_hip_debug_set_knob(gaml_hip_ctx* c, int knob, int value) {
-  if (!c || knob < 0 || knob >= 25) return GAML_HIP_EINVAL;
+  if (!c || knob < 0 || knob >= GAML_HIP_KNOB_COUNT) return GAML_HIP_EINVAL;
   if (c->multi) { for (int k = 0; k < gaml::multi_num_shards(c->multi); k++) gaml::multi_shard(c->multi, k)->knobs[knob] = value; return GAML_HIP_OK; }
   c->knobs[knob] = value;
   return GAML_HIP_OK;
@@ -311,7 +311,7 @@ int gaml_hip_debug_tables_check(gaml_hip_ctx* c, int rs, int64_t* out8) {
     for (Window& w : hm[mt].wins) if (w.dfirst < 0) { w.count = 0; }
   }
   PairTables pt;
-  build_pair_tables(hm[0], hm[1], pt, KNOB(c, 16) != 1, paired_static_ins_n(c, s));
+  build_pair_tables(hm[0], hm[1], pt, KNOB(c, KEEP_DOMINATED) != 1, paired_static_ins_n(c, s));
   const int64_t n = s.mate[0].n_local();
   int64_t compared = 0, bad = 0;
   auto fetch = [&](const DevBuf& d, size_t bytes, std::vector<char>& out) -> int {
@@ -411,7 +411,7 @@ int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* c, int rs, int64_t* out, in
 // waits for the stream and copies back. The reference: build_pair_tables on a copy of the device pool over the windows the
 // live tables and their lists took in (TableDev::held: the build's windows, then every window paired_delta_apply was
 // given), which yields every read's records per mate in (window id, position) order without the always-overwritten
-// junction records (knob 16 as the tables were built). While a rebuild runs beside the evaluations this covers the live
+// junction records (KEEP_DOMINATED as the tables were built). While a rebuild runs beside the evaluations this covers the live
 // tables and lists only. out12 = {pairs on the lists, of those from the compact class's static part / its other part /
 // the <= 2-record class / <= 4 / more, pairs at the fixed stride with lists of up to 2 / of 3 to 4 records, long lists
 // (spill area), entries compared, mismatches, records of later windows left out (the device's count)}.

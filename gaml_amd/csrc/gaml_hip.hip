@@ -106,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void stage_copy_kernel(const int4* __restri
 }
 int stage_upload(gaml_hip_ctx* c, Staging& s, int k, void* dst, size_t bytes, hipStream_t st) {
   if (bytes == 0) return 0;
-  if (KNOB(c, 8) == 1 || (bytes & 15) || bytes > ((size_t)1 << 30)) {
+  if (KNOB(c, UPLOAD_ROUTE) == GAML_HIP_UPLOAD_MEMCPY || (bytes & 15) || bytes > ((size_t)1 << 30)) {
     HIP_TRY(c, hipMemcpyAsync(dst, s.host[k].p, bytes, hipMemcpyHostToDevice, st));
     return 0;
   }
@@ -609,7 +609,7 @@ static int warm_general_kernels(gaml_hip_ctx* c) {
   hipLaunchKernelGGL((paired_score_kernel<false, true>), dim3(1), dim3(kBlock), 0, c->stream, a);
   MultiSets ms;
   memset((void*)&ms, 0, sizeof(ms));
-  ms.pad_ = 16;  // (the wave-per-pair blocks are "left out": with no path set in `ms` the block returns at once)
+  ms.skip_classes = 16;  // (the wave-per-pair blocks are "left out": with no path set in `ms` the block returns at once)
   hipLaunchKernelGGL((paired_score_multi_kernel<true>), dim3(1), dim3(kBlock), 0, c->stream, a, ms);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1132,7 +1132,7 @@ static void finisher_order_sum(const double* ps, const int* pz, int n, double* s
 // any doubt -> a real stream sync. Returns whether the spin sufficed.
 static int wait_host_partials(gaml_hip_ctx* c, bool* spun) {
   const double t0 = now_us();
-  bool spin = KNOB(c, 7) == 0 && !c->handles.empty();
+  bool spin = KNOB(c, NO_SPIN) == 0 && !c->handles.empty();
   for (auto& h : c->handles) if (h.kind != 1) spin = false;
   for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0 || !ps->last_host_partials || ps->last_total_blocks == 0) spin = false;
   if (spin) {

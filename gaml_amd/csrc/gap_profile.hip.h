@@ -101,8 +101,8 @@ namespace {
 // may this context take the device route at all (what does not depend on the path set)
 bool gap_device_capable(const gaml_hip_ctx* c) {
   if (c->multi || c->comm || c->device < 0 || c->world != 1 || c->peers != 1) return false;
-  if (KNOB(c, 18) == 1) return false;  // knob 18 = 1: the fallback route (A/B, tests)
-  if (!c->direct_write || KNOB(c, 8) != 0 || KNOB(c, 13) != 0) return false;
+  if (KNOB(c, GAP_FALLBACK) == 1) return false;  // the fallback route (A/B, tests)
+  if (!c->direct_write || KNOB(c, UPLOAD_ROUTE) != 0 || KNOB(c, NO_RESIDENT_TABLES) != 0) return false;
   // a set with a coverage penalty: gap_tables_kernel moves table entries, not the set's coverage layout -- such a context
   // searches through the fallback (whose multi-length steps are batches, one pass each)
   for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0) return false;

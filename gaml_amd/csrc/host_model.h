@@ -367,7 +367,7 @@ class PairedPlanner {
   // and / or suffix of paths with the previous call's (what an annealing move leaves: it edits one or two paths), only
   // the paths in between are looked at: hashing, registration replay, placements, occurrence lists and the table
   // entries that follow from them are O(changed paths). Returns false (and sets *err) on a node id outside the graph.
-  // allow_incremental = false: everything from scratch (first call, knob 12, after the window maxima changed).
+  // allow_incremental = false: everything from scratch (first call, PLAN_WHOLE_SET, after the window maxima changed).
   bool begin(const GraphStore& g, ShortMate mate[2], const int32_t* flat, const int64_t* offs, int32_t n_paths,
              bool allow_incremental, std::string* err);
   void finish(ShortMate mate[2]);          // pass 2 (needs the windows' records / global maxima): occurrence lists

@@ -1613,7 +1613,7 @@ struct SetDev {  // what differs between the path sets of one batch
 // thresholds, no table is read. The bits are cumulative (bit s implies bit s + 1: a set's tables are its
 // predecessor's plus a patch). Null: unknown, every set resolves every pair. Used by the classes with several records
 // per pair and the delta / wave-per-pair blocks; the compact class resolves every set (see its body).
-struct MultiSets { int n; int pad_; const unsigned char* chg[2]; SetDev set[kMaxSets]; };
+struct MultiSets { int n; int skip_classes; const unsigned char* chg[2]; SetDev set[kMaxSets]; };
 
 constexpr int kTfCodes = 16;  // length codes whose per-set thresholds a multi-set block keeps in LDS
 // COV: the launch marks coverage -- the set's bitmap and slot_base table travel too (pair_term, compact_cover and the general
@@ -2044,7 +2044,7 @@ __global__ __launch_bounds__(kBlock, 5) void paired_score_multi_kernel(PairedArg
     for (int s = 0; s < ms.n; s++) { acc_s[s * kBlock + threadIdx.x] = 0.0; acc_z[s * kBlock + threadIdx.x] = 0; }
     __syncthreads();
     const int cls = lb < a.blocks0 ? 0 : lb < a.blocks01 ? 1 : lb < a.blocks012 ? 2 : 3;
-    if ((ms.pad_ >> cls) & 1) {  // timing experiments (tools/): a class of blocks left out, results wrong
+    if ((ms.skip_classes >> cls) & 1) {  // a class of blocks left out (bit per class; set by the warm-up launch only, for bit 4 below)
       if (threadIdx.x == 0) for (int s = 0; s < ms.n; s++) { ms.set[s].part_sum[lb] = 0.0; ms.set[s].part_zero[lb] = 0; }
       return;
     }
@@ -2087,7 +2087,7 @@ __global__ __launch_bounds__(kBlock, 5) void paired_score_multi_kernel(PairedArg
     }
     return;
   }
-  if ((ms.pad_ >> 4) & 1) {
+  if ((ms.skip_classes >> 4) & 1) {
     if (threadIdx.x == 0) for (int s = 0; s < ms.n; s++) { ms.set[s].part_sum[lb] = 0.0; ms.set[s].part_zero[lb] = 0; }
     return;
   }

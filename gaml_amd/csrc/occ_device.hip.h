@@ -59,13 +59,13 @@ __global__ void __launch_bounds__(kBlock) occ_scatter_kernel(const OccScatterArg
 
 // the scoring launch of this call goes to the resident copy of the tables (launch_paired)
 bool paired_resident_route(const gaml_hip_ctx* c, const PairedSet& s) {
-  return c->host_results && c->direct_write && KNOB(c, 8) == 0 && KNOB(c, 13) == 0;
+  return c->host_results && c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0 && KNOB(c, NO_RESIDENT_TABLES) == 0;
 }
 
 // after pass 2's occurrence lists (planner.finish): may this call's tables be built on the device?
 bool occdev_route_ok(const gaml_hip_ctx* c, PairedSet& s) {
   PairedSet::OccDev& D = s.occdev;
-  if (!c->occ_route || KNOB(c, 17) != 0 || !paired_resident_route(c, s) || !s.persist.valid) return false;
+  if (!c->occ_route || KNOB(c, NO_OCC_DEVICE) != 0 || !paired_resident_route(c, s) || !s.persist.valid) return false;
   if (s.cfg.penalty_constant > 0) return false;  // (the scatter kernel knows nothing of the coverage layout: penalised whole-set calls keep the host route)
   if (s.planner.last_was_incremental()) return false;
   const std::vector<int32_t>& ids = s.planner.ids();

@@ -10,7 +10,7 @@
 // own, one sweep dispatch per launch (launch_paired_multi); the wait is then a real stream wait, one per chunk.
 // ---------------------------------------------------------------------------------------------------------
 static bool batch_fast_capable(const gaml_hip_ctx* c) {
-  if (c->handles.empty() || KNOB(c, 11) == 1) return false;  // knob 11 = 1: force the sequential path (A/B, tools/)
+  if (c->handles.empty() || KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_SEQUENTIAL) return false;  // force the sequential path (A/B, tools/)
   for (auto& h : c->handles) if (h.kind != 1) return false;
   for (auto& ps : c->paireds) if (!paired_multi_capable(c, *ps)) return false;
   return true;
@@ -24,7 +24,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
                                double* partials_out, int32_t* tls) {
   hipStream_t st = c->stream;
   const size_t nps = c->paireds.size();
-  if (!c->direct_write || KNOB(c, 8) != 0 || KNOB(c, 13) != 0 || KNOB(c, 11) == 2) return 1;  // knob 11 = 2: full tables per set (A/B)
+  if (!c->direct_write || KNOB(c, UPLOAD_ROUTE) != 0 || KNOB(c, NO_RESIDENT_TABLES) != 0 || KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_FULL_TABLES) return 1;  // full tables per set (A/B)
   constexpr size_t kPatchCap = 8192;  // entries per read set and batch
   struct PerSet {
     int slot = 0; char* wp = nullptr; size_t stride = 0;
@@ -117,7 +117,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
       HIP_TRY(c, hipGetLastError());
       const unsigned char* chg[2] = {ta.chg[0], ta.chg[1]};
       if (int e = launch_paired_multi(c, ps, launched, upto - launched, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.dev[r.slot], r.stride, st,
-                                      KNOB(c, 11) == 3 ? nullptr : chg)) return e;  // knob 11 = 3: every set resolves every pair (A/B)
+                                      KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_NO_CAPTURE ? nullptr : chg)) return e;  // every set resolves every pair (A/B)
     }
     launched = upto;
     return 0;

@@ -74,9 +74,9 @@ int prepare_paired_tables(gaml_hip_ctx* c, PairedSet& s) {
 // pass 1: window registration / alignment of missing windows and the placement of cached windows
 // (memoised per distinct path: PairedPlanner)
 int prepare_paired_structure(gaml_hip_ctx* c, PairedSet& s, const int32_t* flat, const int64_t* offs, int32_t n_paths) {
-  // knob 12 = 1 forces whole-set planning for A/B runs and tests. (A coverage penalty does not: the table entries carry the
+  // PLAN_WHOLE_SET forces whole-set planning for A/B runs and tests. (A coverage penalty does not: the table entries carry the
   // path slot, and pass 2 lays the bitmap out by slot for the marks and by position for the sweep.)
-  const bool incremental = KNOB(c, 12) == 0;
+  const bool incremental = KNOB(c, PLAN_WHOLE_SET) == 0;
   std::string err;
   if (!s.planner.begin(c->g, s.mate, flat, offs, n_paths, incremental, &err)) return fail(c, GAML_HIP_EINVAL, err);
   return 0;
@@ -207,14 +207,14 @@ void paired_pack(const PairedSet& s, const PairedPrep& p, const PairedLayout& L,
 // the arena: a ring of slots holding per-call tables. On a large-BAR device (MI355X) a slot is fine-grained device
 // memory that the host fills with plain stores through the PCIe BAR (write-combined: 96 KB in ~2 us,
 // tools/bar_write_probe.hip) -- no staging buffer, no copy command, no copy kernel in front of the scoring launch.
-// Otherwise (or knob 8 != 0): pinned staging slot + hipMemcpyAsync (knob 8 = 1) / copy kernel (knob 8 = 2).
+// Otherwise (or UPLOAD_ROUTE != 0): pinned staging slot + hipMemcpyAsync (MEMCPY) / copy kernel (COPY_KERNEL).
 // ---------------------------------------------------------------------------------------------------------
 int arena_acquire(gaml_hip_ctx* c, Arena& A, size_t bytes, hipStream_t st, int* slot_out, char** write_ptr) {
   const int k = A.next;
   A.next = (A.next + 1) % kRing;
   if (A.armed[k]) { HIP_TRY(c, hipEventSynchronize(A.done[k])); A.armed[k] = false; }
   if (!A.done[k]) HIP_TRY(c, hipEventCreateWithFlags(&A.done[k], hipEventDisableTiming));
-  const bool direct = c->direct_write && KNOB(c, 8) == 0;
+  const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
   if (bytes > A.cap[k] || A.direct[k] != direct) {
     HIP_TRY(c, hipStreamSynchronize(st));
     if (A.dev[k]) { HIP_TRY(c, hipFree(A.dev[k])); A.dev[k] = nullptr; A.cap[k] = 0; }
@@ -233,7 +233,7 @@ int arena_acquire(gaml_hip_ctx* c, Arena& A, size_t bytes, hipStream_t st, int* 
 int arena_commit(gaml_hip_ctx* c, Arena& A, int k, size_t bytes, hipStream_t st) {
   if (A.direct[k]) { _mm_sfence(); return 0; }  // drain the write-combining buffers; the doorbell write of the launch orders behind them
   if (bytes == 0) return 0;
-  if (KNOB(c, 8) == 1 || (bytes & 15)) { HIP_TRY(c, hipMemcpyAsync(A.dev[k], A.host[k].p, bytes, hipMemcpyHostToDevice, st)); return 0; }
+  if (KNOB(c, UPLOAD_ROUTE) == GAML_HIP_UPLOAD_MEMCPY || (bytes & 15)) { HIP_TRY(c, hipMemcpyAsync(A.dev[k], A.host[k].p, bytes, hipMemcpyHostToDevice, st)); return 0; }
   const int n16 = (int)(bytes / 16);
   hipLaunchKernelGGL(stage_copy_kernel, dim3((unsigned)std::min(64, (n16 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                      (const int4*)A.host[k].dev, (int4*)A.dev[k], n16);
@@ -408,16 +408,16 @@ void paired_base_args(gaml_hip_ctx* c, PairedSet& s, PairedArgs& a, GridPlan& gp
   // The two parts of class 0 get blocks of their own (PairedArgs::blocks0a): the first by the rule above; the second --
   // a few per cent of the pairs, one more round trip per pair -- a lane per pair up to a third of that.
   const int64_t one_round = (n0a + 4 * kBlock - 1) / (4 * kBlock);
-  const int cap0 = KNOB(c, 0) > 0 ? KNOB(c, 0)
+  const int cap0 = KNOB(c, GRID_CAP_COMPACT) > 0 ? KNOB(c, GRID_CAP_COMPACT)
                                    : (int)std::min<int64_t>(kMaxBlocks, one_round > 768 && one_round <= 1280 ? one_round : std::max<int64_t>(768, n0 / 2900));
   gp.blocks0a = n0a > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>((n0a + 2 * kBlock - 1) / (2 * kBlock), cap0)) : 0;
-  const int cap0b = KNOB(c, 20) > 0 ? KNOB(c, 20) : std::max(1, n0a > 0 ? cap0 / 3 : cap0);
+  const int cap0b = KNOB(c, GRID_CAP_COMPACT_REST) > 0 ? KNOB(c, GRID_CAP_COMPACT_REST) : std::max(1, n0a > 0 ? cap0 / 3 : cap0);
   const int64_t blocks0b = n0b > 0 ? std::max<int64_t>(1, std::min<int64_t>(n0a > 0 ? (n0b + kBlock - 1) / kBlock : (n0b + 2 * kBlock - 1) / (2 * kBlock), cap0b)) : 0;
   gp.blocks0 = (int)std::max<int64_t>(1, gp.blocks0a + blocks0b);
   // the 2-record class: a third of the compact class's blocks (one block per CU at cfg3), lanes take 1-2 pairs; more
   // blocks only crowd the compact class out (tools/blocks_sweep.py at cfg3, pairs ordered by window in every class:
   // 128 blocks 11.4 us, 192: 10.1, 224-256: 9.8-9.9, 320: 10.2)
-  const int cap1 = KNOB(c, 10) > 0 ? KNOB(c, 10) : cap0 / 3;
+  const int cap1 = KNOB(c, GRID_CAP_CLASS1) > 0 ? KNOB(c, GRID_CAP_CLASS1) : cap0 / 3;
   gp.blocks1 = (int)std::max<int64_t>(1, std::min<int64_t>((n01 - n0 + kBlock - 1) / kBlock, cap1));
   gp.blocks2 = (int)std::max<int64_t>(1, std::min<int64_t>((n_main - n01 + kBlock - 1) / kBlock, kMaxBlocks / 4));
   // delta pairs: one lane per pair behind the table classes
@@ -569,7 +569,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   paired_apply_set(a, sd);
   a.out = out4;
   a.timeline = nullptr;
-  const bool timeline = KNOB(c, 3) == 8;
+  const bool timeline = KNOB(c, TIMELINE) == 8;
   if (timeline) {  // in-kernel timeline (tools/kernel_timeline.py): stamps land in mapped host memory
     HIP_TRY(c, s.h_timeline.reserve((size_t)(4 * kMaxBlocks + kOvfMaxBlocks + 256) * (kBlock / 64) * 8 * sizeof(unsigned long long)));
     memset(s.h_timeline.p, 0, s.h_timeline.cap);
@@ -581,10 +581,10 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   if (n > 0) {
     // HIP events bracket the dominant kernel only (bench.py's roofline; rocprofv3 must agree)
     if (c->event_timing && (c->event_tick++ % c->event_every) == 0) { if (int e = take_events(c, &ev)) return e; }
-    // 0 (knob 2 = 1): the block that draws the last ticket adds the partials up (two-level tickets, grid_finish: the ~1,000 blocks
+    // 0 (FINISH_MODE = LAST_BLOCK): the block that draws the last ticket adds the partials up (two-level tickets, grid_finish: the ~1,000 blocks
     // end together and their atomics on 17 words still take 10 us -- a finisher dispatch costs less); 1: finisher kernel
     // (stream-ordered calls; always when a second launch shares the partials); 2: the host adds them (blocking calls)
-    int fin_mode = c->host_results ? 2 : (KNOB(c, 2) ? KNOB(c, 2) - 1 : 1);
+    int fin_mode = c->host_results ? 2 : (KNOB(c, FINISH_MODE) ? KNOB(c, FINISH_MODE) - 1 : 1);
     // a sharded evaluation's status words are written by whatever finishes the partials on the device
     double* status_out = nullptr;
     if (fin_mode != 2 && c->status_dst && !c->status_done) { status_out = c->status_dst; c->status_done = true; }
@@ -596,14 +596,14 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     // markers around the launch would add the marker packets' processing to the interval: an EMPTY kernel
     // of this grid reads 6 us that way (tools/stream_floor.hip).
     hipEvent_t e0 = ev ? ev->first : nullptr, e1 = ev ? ev->second : nullptr;
-#define GAML_LAUNCH_SCORE(...) hipExtLaunchKernelGGL((paired_score_kernel<__VA_ARGS__>), grid, block, KNOB(c, 1), st, e0, e1, 0, a)
+#define GAML_LAUNCH_SCORE(...) hipExtLaunchKernelGGL((paired_score_kernel<__VA_ARGS__>), grid, block, KNOB(c, SCORE_LDS_BYTES), st, e0, e1, 0, a)
 #ifdef GAML_HIP_DEV
     if (timeline) GAML_LAUNCH_SCORE(false, false, true);  // (the instantiation with in-kernel stamps: development builds only)
     else
 #endif
     if (gen_set) { if (fin_mode) GAML_LAUNCH_SCORE(false, true); else GAML_LAUNCH_SCORE(true, true); }
     // a penalised set (no repeated windows, memo present): class 0 marks from the memo / streamed-value bodies
-    else if (cov && a.memo && KNOB(c, 21) == 0) { if (fin_mode) GAML_LAUNCH_SCORE(false, false, false, true); else GAML_LAUNCH_SCORE(true, false, false, true); }
+    else if (cov && a.memo && KNOB(c, NO_COV_INSTANCE) == 0) { if (fin_mode) GAML_LAUNCH_SCORE(false, false, false, true); else GAML_LAUNCH_SCORE(true, false, false, true); }
     else if (fin_mode) GAML_LAUNCH_SCORE(false, false);
     else GAML_LAUNCH_SCORE(true, false);
 #undef GAML_LAUNCH_SCORE
@@ -652,10 +652,10 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
 // behind the scoring launch one sweep dispatch for all sets and one that hands the counters to the host.
 // ---------------------------------------------------------------------------------------------------------
 bool paired_multi_capable(const gaml_hip_ctx* c, const PairedSet& s) {
-  if (KNOB(c, 3) != 0 || KNOB(c, 4) != 0 || !s.floor_positive) return false;
-  // a penalised set: under the conditions of the single call's COV instantiation (knob 21 = 1, class 0 in its general form:
+  if (KNOB(c, TIMELINE) != 0 || KNOB(c, NO_MEMO) != 0 || !s.floor_positive) return false;
+  // a penalised set: under the conditions of the single call's COV instantiation (NO_COV_INSTANCE, class 0 in its general form:
   // the sequential path)
-  return !(s.cfg.penalty_constant > 0) || KNOB(c, 21) == 0;
+  return !(s.cfg.penalty_constant > 0) || KNOB(c, NO_COV_INSTANCE) == 0;
 }
 
 // Sets [first, first + n_sets) of a batch (L / preps / total_lens / arena regions / partial regions are indexed by the
@@ -701,8 +701,7 @@ int launch_paired_multi(gaml_hip_ctx* c, PairedSet& s, int first, int n_sets, co
   MultiSets ms;
   memset(&ms, 0, sizeof(ms));
   ms.n = n_sets;
-  if (KNOB(c, 11) >= 32) ms.pad_ = (KNOB(c, 11) - 32) & 31;  // timing experiments: leave out classes of blocks (bits: compact, <=2, <=4, delta, wave-per-pair)
-  if (chg && KNOB(c, 11) < 64 && !cov) { ms.chg[0] = chg[0]; ms.chg[1] = chg[1]; }  // (a penalised launch runs without the capture: paired_score_multi_kernel)  // (>= 64: and every set resolves every pair)  // (which table entries differ between the sets: only a batch built from patches knows)
+  if (chg && !cov) { ms.chg[0] = chg[0]; ms.chg[1] = chg[1]; }  // (a penalised launch runs without the capture: paired_score_multi_kernel)  // (which table entries differ between the sets: only a batch built from patches knows)
   for (int k = 0; k < n_sets; k++) {
     const int g = first + k;  // the set's number in the batch
     paired_set_view(s, L[g], arena + (size_t)g * stride, total_lens[g], ms.set[k]);

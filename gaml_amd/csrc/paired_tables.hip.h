@@ -140,7 +140,7 @@ int paired_upload_statics(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
   // memo of the pair terms a single-term pair can take (first 4 length combinations, edits < 7, every tabulated distance):
   // nothing in it depends on a path set or on the records
   s.memo_codes = 0;
-  if (KNOB(c, 4) == 0 && s.floor_positive && !s.pt.len_combo.empty() && !s.ins_tab.empty()) {
+  if (KNOB(c, NO_MEMO) == 0 && s.floor_positive && !s.pt.len_combo.empty() && !s.ins_tab.empty()) {
     const int codes = (int)std::min<size_t>(s.pt.len_combo.size(), kMemoCodes);
     const size_t entries = (size_t)codes * 49 * s.ins_tab.size();
     if (entries <= kMemoMaxEntries) {
@@ -156,16 +156,16 @@ int paired_upload_statics(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
   return 0;
 }
 
-// the table length the static memo indices of class 0 are built over, 0: none -- no memo (knob 4, or a floor of 0: the
-// reference then takes log(0)), or knob 19 = 1 (A/B: every class-0 pair resolved per call)
+// the table length the static memo indices of class 0 are built over, 0: none -- no memo (NO_MEMO, or a floor of 0: the
+// reference then takes log(0)), or NO_STATIC_INDEX (A/B: every class-0 pair resolved per call)
 int paired_static_ins_n(const gaml_hip_ctx* c, const PairedSet& s) {
-  return (KNOB(c, 4) == 0 && KNOB(c, 19) == 0 && s.floor_positive && s.memo_codes > 0) ? (int)s.ins_tab.size() : 0;
+  return (KNOB(c, NO_MEMO) == 0 && KNOB(c, NO_STATIC_INDEX) == 0 && s.floor_positive && s.memo_codes > 0) ? (int)s.ins_tab.size() : 0;
 }
 
 // a rebuild is also when windows that no scored path set has used since the previous rebuild leave the device tables
-// (knob 15 = 1: never). The current path set's windows stay, whatever their marks.
+// (NO_RETIRE: never). The current path set's windows stay, whatever their marks.
 void paired_retire_windows(gaml_hip_ctx* c, PairedSet& s) {
-  if (KNOB(c, 15) == 1) return;
+  if (KNOB(c, NO_RETIRE) == 1) return;
   s.planner.mark_used(s.mate, s.image);
   int64_t n = 0;
   for (int mt = 0; mt < 2; mt++) n += s.mate[mt].retire_unused();
@@ -224,7 +224,7 @@ int paired_build_enqueue(gaml_hip_ctx* c, PairedSet& s, TableDev& T, hipStream_t
   gate.from = slice_from; gate.to = slice_to;
   auto in = [&]() { return gate(); };
   if (in()) {
-    const bool fold = KNOB(c, 16) != 1;
+    const bool fold = KNOB(c, KEEP_DOMINATED) != 1;
     T.keep_dominated = !fold;
     T.built = false; T.ros_valid = false;
     HIP_TRY(c, T.cnt.reserve(kTbInts * sizeof(int)));
@@ -415,7 +415,7 @@ int paired_reserve_delta(gaml_hip_ctx* c, PairedSet& s) {
   s.delta_cap = (size_t)std::max<int64_t>(4096, np_all / 2) + 8192;
   s.cap_spill = (size_t)(65536 + np_all / 16);
   s.cap_sprec = (size_t)((2 << 20) + np_all);
-  if (KNOB(c, 24) > 0) { s.cap_spill = (size_t)KNOB(c, 24); s.cap_sprec = (size_t)16 * (size_t)KNOB(c, 24); }  // knob 24 = n: room for n long lists, 16 n records per mate (tests of the overflow path)
+  if (KNOB(c, DELTA_SPILL_CAP) > 0) { s.cap_spill = (size_t)KNOB(c, DELTA_SPILL_CAP); s.cap_sprec = (size_t)16 * (size_t)KNOB(c, DELTA_SPILL_CAP); }  // room for n long lists, 16 n records per mate (tests of the overflow path)
   HIP_TRY(c, s.dl_slot.reserve(s.delta_cap * sizeof(int32_t)));
   HIP_TRY(c, s.dl_spill.reserve(s.delta_cap * sizeof(int32_t)));
   for (int mt = 0; mt < 2; mt++) {
@@ -460,7 +460,7 @@ bool paired_delta_overflowed(const PairedSet& s) {
 int paired_delta_apply(gaml_hip_ctx* c, PairedSet& s, TableDev& T, std::vector<std::pair<int32_t, int32_t>>& wins, hipStream_t st) {
   if (wins.empty()) return 0;
   if (int e = paired_reserve_delta(c, s)) return e;
-  const bool fold = KNOB(c, 16) != 1;
+  const bool fold = KNOB(c, KEEP_DOMINATED) != 1;
   std::sort(wins.begin(), wins.end());  // mate 0's windows first, each mate's by window id: a pair's new records arrive in table order
   DlArgs a;
   memset(&a, 0, sizeof(a));
@@ -480,7 +480,7 @@ int paired_delta_apply(gaml_hip_ctx* c, PairedSet& s, TableDev& T, std::vector<s
   a.bins = s.dl_bins.as<unsigned long long>(); a.bin_count = s.dl_bin_count.as<int>(); a.blk_tot = s.dl_blk_tot.as<int>();
   int64_t all_records = 0;
   for (const auto& mw : wins) all_records += s.mate[mw.first].wins[mw.second].count;
-  const bool multi_block = (all_records > 3000 || wins.size() > (size_t)kDlMaxWins) && KNOB(c, 22) != 1;  // knob 22 = 1: one-block launches only (A/B, tests)
+  const bool multi_block = (all_records > 3000 || wins.size() > (size_t)kDlMaxWins) && KNOB(c, DELTA_ONE_BLOCK) != 1;  // one-block launches only (A/B, tests)
   const int max_recs = multi_block ? kDlMbMaxRecs : kDlMaxRecs;
   std::vector<DlWin> big;  // a multi-block launch's window list when the argument block cannot hold it
 #ifdef GAML_HIP_DEV
@@ -641,7 +641,7 @@ int paired_prereserve(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
   const int64_t A2[2] = {std::max<int64_t>(paired_records_cap(s, 0), 2 * n + 65536), std::max<int64_t>(paired_records_cap(s, 1), 2 * n + 65536)};
   if (first) { for (int mt = 0; mt < 2; mt++) { if (int e = pool_reserve(c, s, mt, n + n / 8)) return e; } }
   if (first || !s.tab.rec8[0].p) { if (int e = paired_reserve_tabledev(c, s.tab, n, A2)) return e; }
-  if ((first || !rb.tab.rec8[0].p) && KNOB(c, 14) != 1) { if (int e = paired_reserve_tabledev(c, rb.tab, n, A2)) return e; }
+  if ((first || !rb.tab.rec8[0].p) && KNOB(c, REBUILD_ON_CALLER) == 0) { if (int e = paired_reserve_tabledev(c, rb.tab, n, A2)) return e; }
   if (first || !B.k_in.p) {
     const size_t maxA = (size_t)std::max<int64_t>(std::max(A2[0], A2[1]), n);
     HIP_TRY(c, B.k_in.reserve(maxA * sizeof(rs_u64))); HIP_TRY(c, B.k_out.reserve(maxA * sizeof(rs_u64))); HIP_TRY(c, B.k_tmp.reserve(maxA * sizeof(rs_u64)));
@@ -665,7 +665,7 @@ int paired_prereserve(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
     HIP_TRY(c, s.stage_pool.host[k].reserve((size_t)1 << 20));
     if (!s.stage_pool.done[k]) HIP_TRY(c, hipEventCreateWithFlags(&s.stage_pool.done[k], hipEventDisableTiming));
   }
-  if (KNOB(c, 14) != 1) {
+  if (KNOB(c, REBUILD_ON_CALLER) == 0) {
     if (!rb.stream) HIP_TRY(c, paired_build_stream(&rb.stream));
     if (!rb.done) HIP_TRY(c, hipEventCreateWithFlags(&rb.done, hipEventDisableTiming));
     if (!rb.mark) HIP_TRY(c, hipEventCreateWithFlags(&rb.mark, hipEventDisableTiming));
@@ -797,7 +797,7 @@ int paired_sync_tables(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
   // The new tables take over a FIXED number of evaluations after their build was started -- not whenever the build
   // happens to be done: a rebuild changes the order of the final sum (last bits), and equal inputs must give equal outputs
   // run to run (the annealing loop compares likelihoods with strict >).
-  const int64_t swap_after = KNOB(c, 14) > 1 ? KNOB(c, 14) : kTakeOverAfter;
+  const int64_t swap_after = KNOB(c, TAKE_OVER_AFTER) > 0 ? KNOB(c, TAKE_OVER_AFTER) : kTakeOverAfter;
   if (rb.active && s.eval_count - rb.start_eval >= swap_after) { if (int e = paired_finish_async_rebuild(c, s, st)) return e; }
   else if (rb.active) { if (int e = paired_build_continue(c, s, false)) return e; }
   bool activated_now = !s.mate[0].activated_log.empty() || !s.mate[1].activated_log.empty();
@@ -806,15 +806,15 @@ int paired_sync_tables(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
   // Windows activated since the tables were built put their pairs on the delta lists. The tables are rebuilt when the
   // lists pass pairs / 8, when the cache has been quiet for 64 evaluations with pairs still on the lists, or on request
   // (gaml_hip_compact_tables: at the next evaluation, on the calling stream).
-  const int64_t limit = KNOB(c, 6) == 1 ? 0 : (KNOB(c, 18) > 1 ? std::max<int64_t>(256, np / KNOB(c, 18)) : std::max<int64_t>(4096, np / 8));  // (knob 18 > 1: tests and soaks want rebuilds at small sizes; 1 is the gap profile's switch)
+  const int64_t limit = KNOB(c, DELTA_POLICY) == GAML_HIP_DELTA_NO_LISTS ? 0 : (KNOB(c, REBUILD_DIVISOR) > 1 ? std::max<int64_t>(256, np / KNOB(c, REBUILD_DIVISOR)) : std::max<int64_t>(4096, np / 8));  // (tests and soaks want rebuilds at small sizes)
   int64_t new_records = 0;
   if (activated_now) for (int mt = 0; mt < 2; mt++) for (int32_t w : s.mate[mt].activated_log) new_records += s.mate[mt].wins[w].count;
   const bool over = activated_now && s.nd_est + new_records > limit;
-  const bool quiet = !activated_now && s.nd_est > 0 && s.quiet_calls >= 64 && KNOB(c, 6) != 2;
-  const bool refold = (KNOB(c, 16) == 1) != s.tab.keep_dominated;  // A/B of the table contents: a request rebuilds even without delta pairs
+  const bool quiet = !activated_now && s.nd_est > 0 && s.quiet_calls >= 64 && KNOB(c, DELTA_POLICY) != GAML_HIP_DELTA_NO_QUIET_REBUILD;
+  const bool refold = (KNOB(c, KEEP_DOMINATED) == 1) != s.tab.keep_dominated;  // A/B of the table contents: a request rebuilds even without delta pairs
   const bool asked = s.compact_requested && (s.nd_est > 0 || activated_now || refold);
   s.compact_requested = false;
-  const bool beside = KNOB(c, 14) != 1 && KNOB(c, 6) != 1;
+  const bool beside = KNOB(c, REBUILD_ON_CALLER) == 0 && KNOB(c, DELTA_POLICY) != GAML_HIP_DELTA_NO_LISTS;
   const int64_t hard = s.delta_cap ? (int64_t)s.delta_cap - 2048 : std::max<int64_t>(4096, np / 2);
   const bool too_many = s.nd_est + new_records > hard || new_records > kDeltaMaxPerCall;
   if (asked || ((over || quiet) && !beside) || too_many) {

@@ -378,7 +378,7 @@ int64_t gaml_hip_align_window(gaml_hip_ctx* ctx, int readset, int mate, const in
  * The device aligns the windows of a paired set's mate whose reads have at most 510 bases and whose indexed read
  * length is at least 16; every other mate, single-end sets and host-only contexts are served by the library's host
  * aligner with identical records, and do not count here -- counters that stay at zero mean the host aligner ran.
- * (Development builds: knob 5 = 1, gaml_hip_debug.h, forces the host aligner.) */
+ * (Development builds: GAML_HIP_KNOB_ALIGNER_ROUTE = GAML_HIP_ALIGNER_HOST, gaml_hip_debug.h, forces the host aligner.) */
 int gaml_hip_aligner_stats(gaml_hip_ctx* ctx, int64_t* windows, int64_t* candidates, double* microseconds);
 /* the same time by stage, host clock, cumulative: out6 = {window strings + upload, spans + candidates (small batches: the
  * whole device pipeline up to the published headers), extension, hits to the host, ordering + filing on the host, batches} */

@@ -59,39 +59,79 @@ int32_t gaml_hip_debug_cov_layout(gaml_hip_ctx* ctx, int readset, int32_t* slot_
 /* node ids of a cached window (by id); returns its length, -1 if the id is unknown */
 int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int32_t window_id, int32_t* out, int32_t cap);
 /* ---- tuning ------------------------------------------------------------------------------------- */
-/* tuning experiments and A/B switches (tools/, tests): 0 = compact-class blocks, 1 = dynamic LDS bytes, 2 = finish mode of
- * stream-ordered calls (1 two-level tickets in the kernel, 2 finisher kernel = the default), 3 = 8: in-kernel timeline,
- * 4 = 1: no floor/log memo, 5 = window aligner: 1 host, 2 hits sorted on the host, 3 always the general route, 4 one
- * small-batch pipeline per mate, 5 window strings through the input block, 6 hits filed on the host (default: on the
- * device), 6 = 1: no delta lists (every newly activated window rebuilds the tables), 2: no quiet-spell rebuild, 7 = 1:
- * always wait with hipStreamSynchronize (no spinning on the pinned partials), 8 = 1: no direct writes through the BAR
- * (staging slots + copies), 9 = 1: aligner stage times with device syncs, 10 = blocks of the <=2-record class, 11 =
- * batches: 1 one launch per path set, 2 whole tables per set, 3 no capture of unchanged pairs, 32 + mask: classes of
- * blocks left out (TIMING ONLY, results wrong), 12 = 1: every path set planned from scratch, 13 = 1: whole per-call tables
- * through the ring (no resident copy), 14 = 1: every table build on the calling stream, k > 1: a build beside the
- * evaluations takes over k evaluations after its start (default 96), 15 = 1: rebuilds never retire unused windows,
- * 17 = 1: whole-set calls build their occurrence tables on the host (no device route, occ_device.hip.h),
- * 16 = 1: record tables keep the records that can never survive the overwrite rule (takes effect at the next table build;
- * same values either way), 18 = d > 1: tables are rebuilt when the delta lists pass pairs / d (default 8), 18 = 1: gap profiles take their
- * fallback route (gaml_hip_gap_profile; the rebuild rule stays the default), 19 = 1: no static
- * memo indices (takes effect at the next table build; same values either way), 20 = blocks of the compact class's second
- * part, 21 = 1: a set with a coverage penalty scores its compact class in the general form (three table loads per pair, no
- * streamed values: the route of every penalised set before the marks moved into the memo bodies), 22 = 1: delta maintenance by one-block launches only (default: multi-block
- * above 3,000 records), 23 = n > 0: the window aligner's general route starts with room for n spans and n candidates instead of
- * its estimate from the window bases (its retry loop then grows both; same records either way), 24 = n > 0: the delta store's spill area
- * holds n long lists and 16 n records per mate (read when the store is reserved: set it before the first evaluation; tests of
- * the overflow path). Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */
-/* Ablation 8 (knob 3 = 8) of the last evaluation of paired read set rs: 8 wall-clock stamps (10 ns units) per wave,
+/* The development build's A/B switches and tuning knobs: the one list of them. Every knob is 0 by default, and the release
+ * library is compiled with every one at 0. A number never moves and is never re-used (probes load libraries built from
+ * older trees and address them by number): a new knob takes the next number, before GAML_HIP_KNOB_COUNT. */
+enum gaml_hip_knob {
+  GAML_HIP_KNOB_GRID_CAP_COMPACT = 0,       /* n > 0: most blocks of the compact class (default: from the device's CU count) */
+  GAML_HIP_KNOB_SCORE_LDS_BYTES = 1,        /* n: dynamic LDS bytes on the single-set scoring launch (occupancy experiments) */
+  GAML_HIP_KNOB_FINISH_MODE = 2,            /* gaml_hip_finish_mode: who adds the partials of a stream-ordered call (default: the finisher kernel) */
+  GAML_HIP_KNOB_TIMELINE = 3,               /* 8: in-kernel time stamps (gaml_hip_debug_timeline); any non-zero value keeps batches off the multi-set kernel */
+  GAML_HIP_KNOB_NO_MEMO = 4,                /* 1: no floor/log memo of pair terms */
+  GAML_HIP_KNOB_ALIGNER_ROUTE = 5,          /* gaml_hip_aligner_route: which route the window aligner is held to (default: its own choice per batch) */
+  GAML_HIP_KNOB_DELTA_POLICY = 6,           /* gaml_hip_delta_policy: delta lists off, or no rebuild after a quiet spell */
+  GAML_HIP_KNOB_NO_SPIN = 7,                /* 1: blocking calls wait with hipStreamSynchronize, no spinning on the pinned partials */
+  GAML_HIP_KNOB_UPLOAD_ROUTE = 8,           /* gaml_hip_upload_route: pinned staging slots instead of host stores through the BAR */
+  GAML_HIP_KNOB_ALIGNER_TIMED = 9,          /* 1: device syncs between the aligner's stages, for stage times */
+  GAML_HIP_KNOB_GRID_CAP_CLASS1 = 10,       /* n > 0: most blocks of the <= 2-record class (default: a third of the compact class's) */
+  GAML_HIP_KNOB_BATCH_ROUTE = 11,           /* gaml_hip_batch_route: how gaml_hip_calc_prob_batch scores its path sets (default: one pass, tables from patches) */
+  GAML_HIP_KNOB_PLAN_WHOLE_SET = 12,        /* 1: every path set planned from scratch, no incremental planning */
+  GAML_HIP_KNOB_NO_RESIDENT_TABLES = 13,    /* 1: whole per-call tables through the ring, no resident device copy */
+  GAML_HIP_KNOB_REBUILD_ON_CALLER = 14,     /* 1: every table build on the calling stream, none beside the evaluations */
+  GAML_HIP_KNOB_NO_RETIRE = 15,             /* 1: rebuilds never retire unused windows */
+  GAML_HIP_KNOB_KEEP_DOMINATED = 16,        /* 1: record tables keep the junction records that never survive the overwrite rule (from the next table build; same values) */
+  GAML_HIP_KNOB_NO_OCC_DEVICE = 17,         /* 1: whole-set calls build their occurrence tables on the host (no device route, occ_device.hip.h) */
+  GAML_HIP_KNOB_GAP_FALLBACK = 18,          /* 1: gaml_hip_gap_profile and the gap-length search take their fallback route */
+  GAML_HIP_KNOB_NO_STATIC_INDEX = 19,       /* 1: no static memo indices, every compact-class pair resolved per call (from the next table build; same values) */
+  GAML_HIP_KNOB_GRID_CAP_COMPACT_REST = 20, /* n > 0: most blocks of the compact class's second part */
+  GAML_HIP_KNOB_NO_COV_INSTANCE = 21,       /* 1: a set with a coverage penalty scores its compact class in the general form (three table loads per pair, no streamed values) */
+  GAML_HIP_KNOB_DELTA_ONE_BLOCK = 22,       /* 1: delta maintenance by one-block launches only (default: multi-block above 3,000 records) */
+  GAML_HIP_KNOB_ALIGNER_FIRST_CAP = 23,     /* n > 0: the aligner's general route starts with room for n spans and n candidates (its retry loop grows both; same records) */
+  GAML_HIP_KNOB_DELTA_SPILL_CAP = 24,       /* n > 0: the delta store's spill area holds n long lists, 16 n records per mate (read when the store is reserved: set it before the first evaluation) */
+  GAML_HIP_KNOB_TAKE_OVER_AFTER = 25,       /* n > 0: a build beside the evaluations takes over n evaluations after its start (default 96) */
+  GAML_HIP_KNOB_REBUILD_DIVISOR = 26,       /* n > 1: tables are rebuilt when the delta lists pass pairs / n, at least 256 (default: pairs / 8, at least 4,096) */
+  GAML_HIP_KNOB_COUNT = 27
+};
+/* the values of the knobs that choose between routes (0 = the default, in every one) */
+enum gaml_hip_finish_mode {
+  GAML_HIP_FINISH_LAST_BLOCK = 1,  /* the block that draws the last ticket adds the partials up (two-level tickets in the kernel) */
+  GAML_HIP_FINISH_KERNEL = 2       /* a finisher kernel does: the default, spelled out */
+};
+enum gaml_hip_aligner_route {
+  GAML_HIP_ALIGNER_HOST = 1,         /* the host aligner */
+  GAML_HIP_ALIGNER_HOST_SORT = 2,    /* the hits of large batches sorted on the host */
+  GAML_HIP_ALIGNER_GENERAL = 3,      /* always the general route, no small-batch pipeline */
+  GAML_HIP_ALIGNER_PER_MATE = 4,     /* one small-batch pipeline per mate */
+  GAML_HIP_ALIGNER_INPUT_BLOCK = 5,  /* window strings always through the input block, never the kernel arguments */
+  GAML_HIP_ALIGNER_HOST_FILING = 6   /* hits filed on the host */
+};
+enum gaml_hip_delta_policy {
+  GAML_HIP_DELTA_NO_LISTS = 1,         /* no delta lists: every newly activated window rebuilds the tables, on the calling stream */
+  GAML_HIP_DELTA_NO_QUIET_REBUILD = 2  /* no rebuild after 64 calls without an activation */
+};
+enum gaml_hip_upload_route {
+  GAML_HIP_UPLOAD_MEMCPY = 1,      /* pinned staging slot + hipMemcpyAsync */
+  GAML_HIP_UPLOAD_COPY_KERNEL = 2  /* pinned staging slot + copy kernel */
+};
+enum gaml_hip_batch_route {
+  GAML_HIP_BATCH_SEQUENTIAL = 1,   /* one launch per path set */
+  GAML_HIP_BATCH_FULL_TABLES = 2,  /* one pass, whole tables per set */
+  GAML_HIP_BATCH_NO_CAPTURE = 3    /* one pass, every set resolves every pair (no capture of unchanged pairs) */
+};
+/* `knob` is a gaml_hip_knob (an int in the signature: a probe may address a library built from an older tree by number);
+ * GAML_HIP_EINVAL outside 0 .. GAML_HIP_KNOB_COUNT - 1. A multi-device context passes the value on to every shard.
+ * Environment (development build): GAML_DL_STAMPS=1 prints the delta kernel's stage times. */
+int gaml_hip_debug_set_knob(gaml_hip_ctx* ctx, int knob, int value);
+/* Ablation 8 (GAML_HIP_KNOB_TIMELINE = 8) of the last evaluation of paired read set rs: 8 wall-clock stamps (10 ns units) per wave,
  * [kernel entry, tables in LDS, records in, occurrences in, memo in, stores issued, block reduced, class]. Returns the
  * number of waves copied. Tuning aid (tools/kernel_timeline.py). */
 int gaml_hip_debug_timeline(gaml_hip_ctx* ctx, int rs, unsigned long long* out, int64_t cap_waves);
 
-int gaml_hip_debug_set_knob(gaml_hip_ctx* ctx, int knob, int value);
 /* Environment (read once): GAML_HIP_TRACE_HOST=1 -- host-side phase times of slow calls, table builds and rebuilds on
  * stderr; GAML_HIP_TRACE_ALIGNER=1 -- aligner stage times with gaml_hip_aligner_stats; GAML_HIP_BACKTRACE=1 -- a
  * backtrace on stderr when the process aborts or faults (also after the HIP runtime reports a GPU memory fault). */
 /* host-only (works without a device): the record tables of the windows that are active now, built with and without the
- * rule "a junction record that the first node's own record always overwrites stays out" (knob 16), compared pair by
+ * rule "a junction record that the first node's own record always overwrites stays out" (GAML_HIP_KNOB_KEEP_DOMINATED), compared pair by
  * pair. out6 = {records left out mate 1, mate 2, compact-class pairs with / without the rule, records checked,
  * violations}; GAML_HIP_ESTATE if a record was left out that the rule does not cover. */
 int gaml_hip_debug_fold_check(gaml_hip_ctx* ctx, int readset, int64_t* out6);
@@ -135,8 +175,9 @@ int gaml_hip_debug_aligner_routes(gaml_hip_ctx* ctx, int64_t* out4);
 
 /* bad_bases of paired set `readset` for every path set of the last gaml_hip_calc_prob_batch, in the batch's order, whichever
  * route its chunks took (0 for a set without coverage penalty). Returns the number of path sets; at most `cap` are written.
- * A batch over penalised sets: knob 11 = 0 the one-pass routes (tables from patches, else whole; the capture of unchanged
- * pairs is always off for such a launch, so 3 equals 0 there), 2 whole tables per set, 1 one call per path set. */
+ * A batch over penalised sets: GAML_HIP_KNOB_BATCH_ROUTE at 0 takes the one-pass routes (tables from patches, else whole; the
+ * capture of unchanged pairs is always off for such a launch, so NO_CAPTURE equals 0 there), FULL_TABLES whole tables per set,
+ * SEQUENTIAL one call per path set. */
 int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* ctx, int readset, int64_t* out, int32_t cap);
 
 /* The LIVE record tables plus the live delta lists (gaml_amd/csrc/delta_dev.hip.h) of paired set `readset` against the host

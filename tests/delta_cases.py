@@ -1,7 +1,7 @@
 """Inputs shared by the tests of the device delta-list maintenance (tests/test_delta_cases_host.py,
 tests/test_gpu_delta_lists.py): three read sets and, per scenario, a sequence of path sets -- the first builds the record
 tables, every later one activates a chosen group of windows -- together with the launch the maintenance has to choose for
-that group by default and with knob 22 = 1 (gaml_amd/csrc/paired_tables.hip.h paired_delta_apply). Deterministic; numpy only."""
+that group by default and with DELTA_ONE_BLOCK (gaml_amd/csrc/paired_tables.hip.h paired_delta_apply). Deterministic; numpy only."""
 from functools import lru_cache
 
 import numpy as np
@@ -49,7 +49,7 @@ def _solo(nodes):
 
 
 # What a step's activation has to come to, and what paired_delta_apply then launches: (records lo, records hi, windows lo,
-# windows hi, route by default, route with knob 22 = 1). A route is a dict of the counters gaml_hip_debug_delta_routes
+# windows hi, route by default, route with DELTA_ONE_BLOCK). A route is a dict of the counters gaml_hip_debug_delta_routes
 # returns that the step must add ("one", "two", "four", "eight": one-block launches by records per thread; "multi_block",
 # "multi_block_wlist", "windows_cut"); a counter it does not name must not move. A tuple as a value: (at least, at most).
 class Scenario:
@@ -102,7 +102,7 @@ def spill_steps():
 
 # records the steps of spill_steps activate: what each launch needs, (at least, at most)
 SPILL_RECORDS = ((2049, 3000), (1025, 2048), (1025, 2048), (8193, 16384))
-# ... and the launches those make: by default / with knob 22 = 1 (see scenarios())
+# ... and the launches those make: by default / with DELTA_ONE_BLOCK (see scenarios())
 SPILL_ROUTES = (({"four": 1}, {"four": 1}), ({"two": 1}, {"two": 1}), ({"two": 1}, {"two": 1}), ({"multi_block": 1}, {"launches": 2, "windows_cut": 1}))
 
 

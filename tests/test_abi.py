@@ -100,3 +100,53 @@ def test_argument_errors(built):
     with pytest.raises(api.GamlHipError):  # device ordinal that does not exist
         api.Context(device=4096)
     assert "gaml_hip" in api.version()
+
+
+def declared_enums(header="gaml_hip_debug.h"):
+    """{enum name: {enumerator: number}} of a header whose enumerators all carry an explicit number"""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    enums = {}
+    for name, body in re.findall(r"\benum\s+(gaml_hip_[a-z_]+)\s*\{(.*?)\}", text, flags=re.S):
+        entries = [e.strip() for e in body.split(",") if e.strip()]
+        assert all(re.fullmatch(r"GAML_HIP_[A-Z0-9_]+\s*=\s*\d+", e) for e in entries), (name, entries)
+        enums[name] = {e.split("=")[0].strip(): int(e.split("=")[1]) for e in entries}
+    return enums
+
+
+# what the numbers 0-24 meant when the knobs got their names: libraries built from older trees are addressed by these numbers
+KNOBS_0_TO_24 = ["GRID_CAP_COMPACT", "SCORE_LDS_BYTES", "FINISH_MODE", "TIMELINE", "NO_MEMO", "ALIGNER_ROUTE", "DELTA_POLICY", "NO_SPIN",
+                 "UPLOAD_ROUTE", "ALIGNER_TIMED", "GRID_CAP_CLASS1", "BATCH_ROUTE", "PLAN_WHOLE_SET", "NO_RESIDENT_TABLES",
+                 "REBUILD_ON_CALLER", "NO_RETIRE", "KEEP_DOMINATED", "NO_OCC_DEVICE", "GAP_FALLBACK", "NO_STATIC_INDEX",
+                 "GRID_CAP_COMPACT_REST", "NO_COV_INSTANCE", "DELTA_ONE_BLOCK", "ALIGNER_FIRST_CAP", "DELTA_SPILL_CAP"]
+
+
+def test_knob_registry_matches_the_binding_and_keeps_its_numbers(built):
+    """enum gaml_hip_knob (include/gaml_hip_debug.h) is the one list of the development build's knobs: api.Knob repeats it name
+    for name, the numbers run from 0 to GAML_HIP_KNOB_COUNT - 1 without a gap, and 0-24 are what they were -- a new knob
+    takes a new number. The enums of the knobs' named values are repeated in api as well."""
+    from gaml_amd import api
+    enums = declared_enums()
+    knobs = {n[len("GAML_HIP_KNOB_"):]: v for n, v in enums["gaml_hip_knob"].items()}
+    assert len(knobs) == len(enums["gaml_hip_knob"]) and all(n.startswith("GAML_HIP_KNOB_") for n in enums["gaml_hip_knob"])
+    count = knobs.pop("COUNT")
+    assert {k.name: int(k) for k in api.Knob} == knobs and len(api.Knob.__members__) == len(knobs)  # (no alias either)
+    assert sorted(knobs.values()) == list(range(count)) and api.KNOB_COUNT == count
+    assert [api.Knob(i).name for i in range(25)] == KNOBS_0_TO_24
+    values = {"gaml_hip_finish_mode": ("GAML_HIP_FINISH_", api.FinishMode), "gaml_hip_aligner_route": ("GAML_HIP_ALIGNER_", api.AlignerRoute),
+              "gaml_hip_delta_policy": ("GAML_HIP_DELTA_", api.DeltaPolicy), "gaml_hip_upload_route": ("GAML_HIP_UPLOAD_", api.UploadRoute),
+              "gaml_hip_batch_route": ("GAML_HIP_BATCH_", api.BatchRoute)}
+    assert set(enums) == set(values) | {"gaml_hip_knob"}
+    for name, (prefix, cls) in values.items():
+        assert {prefix + v.name: int(v) for v in cls} == enums[name], name
+
+
+def test_set_knob_checks_its_range(built):
+    from gaml_amd import api
+    ctx = api.Context(device=-1)
+    ctx.debug_set_knob(api.Knob(api.KNOB_COUNT - 1), 0)
+    ctx.debug_set_knob(int(api.Knob.NO_MEMO), 0)  # a number still does: what a library built from an older tree is addressed by
+    for knob in (api.KNOB_COUNT, -1):
+        with pytest.raises(api.GamlHipError) as e:
+            ctx.debug_set_knob(knob, 0)
+        assert e.value.code == api.EINVAL, knob

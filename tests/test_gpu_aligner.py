@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 def _ctx(api, gb, go, pr, host_aligner, mean=300.0, sd=30.0):
     ctx = api.Context(device=0)
-    ctx.debug_set_knob(5, 1 if host_aligner else 0)
+    ctx.debug_set_knob(api.Knob.ALIGNER_ROUTE, api.AlignerRoute.HOST if host_aligner else 0)
     ctx.set_graph(gb, go)
     ctx.add_paired(api.paired_cfg(mean, sd), *synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
     return ctx
@@ -87,7 +87,7 @@ def test_gpu_aligner_speed_and_parity_at_cfg2():
 
 def test_small_batch_pipeline_equals_the_general_route():
     """Small batches of new windows (what an annealing move brings) take a one-wait pipeline on the library's stream:
-    both mates in one (aln_pair_small), or one per mate side by side (knob 5 = 4); knob 5 = 3 forces the general route.
+    both mates in one (aln_pair_small), or one per mate side by side (AlignerRoute.PER_MATE); AlignerRoute.GENERAL forces the general route.
     Same records, same values, along an annealing-style walk."""
     from gaml_amd import api
     G, n, seed = 120_000, 6000, 77
@@ -96,8 +96,8 @@ def test_small_batch_pipeline_equals_the_general_route():
     pr = synth.make_paired_reads(genome, n, 150, 300.0, 30.0, 0.01, seed)
     gb, go = g.packed()
     fast, per_mate, general = _ctx(api, gb, go, pr, False), _ctx(api, gb, go, pr, False), _ctx(api, gb, go, pr, False)
-    per_mate.debug_set_knob(5, 4)
-    general.debug_set_knob(5, 3)
+    per_mate.debug_set_knob(api.Knob.ALIGNER_ROUTE, api.AlignerRoute.PER_MATE)
+    general.debug_set_knob(api.Knob.ALIGNER_ROUTE, api.AlignerRoute.GENERAL)
     start, seq = synth.sa_sequence(g, 120, seed=3, threshold=400)
     for ps in [start] + seq:
         a, b, c = fast.calc_prob(ps), general.calc_prob(ps), per_mate.calc_prob(ps)

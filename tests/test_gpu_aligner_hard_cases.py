@@ -13,11 +13,11 @@ from aligner_hard_cases import hard_case, junction_moves, n_collision_case
 pytestmark = pytest.mark.gpu
 
 
-def _ctx(gb, go, reads, mean, sd, knob5=0, knob23=0):
+def _ctx(gb, go, reads, mean, sd, aligner_route=0, first_cap=0):
     from gaml_amd import api
     ctx = api.Context(device=0)
-    ctx.debug_set_knob(5, knob5)
-    ctx.debug_set_knob(23, knob23)
+    ctx.debug_set_knob(api.Knob.ALIGNER_ROUTE, aligner_route)
+    ctx.debug_set_knob(api.Knob.ALIGNER_FIRST_CAP, first_cap)
     ctx.set_graph(gb, go)
     ctx.add_paired(api.paired_cfg(mean, sd), *reads)
     return ctx
@@ -67,7 +67,8 @@ def test_device_equals_host_aligner_and_oracle_on_hard_cases(L):
     g, reads, indel, regions, sets = hard_case(L)
     gb, go = g.packed()
     mean, sd = 2.2 * L, 0.2 * L
-    gpu, cpu = _ctx(gb, go, reads, mean, sd, 0), _ctx(gb, go, reads, mean, sd, 1)
+    from gaml_amd.api import AlignerRoute
+    gpu, cpu = _ctx(gb, go, reads, mean, sd, 0), _ctx(gb, go, reads, mean, sd, AlignerRoute.HOST)
     orc = op.Oracle()
     orc.set_graph(gb, go)
     orc.add_paired(*reads, 0.01, op.paired_cfg(mean, sd))
@@ -104,16 +105,17 @@ def test_device_equals_host_aligner_and_oracle_on_hard_cases(L):
 
 @pytest.mark.parametrize("L,n_dense", [(100, 1500), (300, 3500)])
 def test_routes_agree_on_junction_windows_in_repeats(L, n_dense):
-    """One path per node, then join after join across the planted regions (junction_moves): the paired small batch (knob
-    5 = 0), the general route (3), one small pipeline per mate (4), window strings through the input block (5) and hits
-    filed on the host (6) give bit-equal values and byte-equal records for every window after every step, equal to the
-    host aligner's (1). n_dense is sized so that one step's junction windows hold more than 2,048 records -- so more
+    """One path per node, then join after join across the planted regions (junction_moves): the paired small batch
+    (ALIGNER_ROUTE at 0), the general route (GENERAL), one small pipeline per mate (PER_MATE), window strings through the input
+    block (INPUT_BLOCK) and hits filed on the host (HOST_FILING) give bit-equal values and byte-equal records for every window
+    after every step, equal to the host aligner's (HOST). n_dense is sized so that one step's junction windows hold more than 2,048 records -- so more
     candidates than that: the device filing refuses the batch after the paired pipeline has run and the per-mate route
     redoes it."""
     g, reads, indel, regions, sets = hard_case(L, n_dense=n_dense)
     gb, go = g.packed()
-    knobs = (0, 3, 4, 5, 6, 1)
-    ctxs = [_ctx(gb, go, reads, 2.2 * L, 0.2 * L, k) for k in knobs]
+    from gaml_amd.api import AlignerRoute as R
+    held_to = (0, R.GENERAL, R.PER_MATE, R.INPUT_BLOCK, R.HOST_FILING, R.HOST)
+    ctxs = [_ctx(gb, go, reads, 2.2 * L, 0.2 * L, k) for k in held_to]
     host = ctxs[-1]
     steps = junction_moves(g, regions)
     assert len(steps) >= 5
@@ -127,26 +129,27 @@ def test_routes_agree_on_junction_windows_in_repeats(L, n_dense):
             seen[mate] = host.window_count(0, mate)
         if paths is not steps[0]:
             most = max(most, new)
-    routes = {k: c.debug_aligner_routes() for k, c in zip(knobs, ctxs)}
+    routes = {k: c.debug_aligner_routes() for k, c in zip(held_to, ctxs)}
     print(f"L = {L}: {len(steps)} steps, at most {most} records in a step's new windows, routes {routes}")
     assert most > 2048
-    for k in (0, 5):  # the paired pipeline ran, the filing kernel refused, the per-mate route took over
+    for k in (0, R.INPUT_BLOCK):  # the paired pipeline ran, the filing kernel refused, the per-mate route took over
         assert routes[k]["pair_filing"] > 0
-    for k in (3, 4, 6, 1):
+    for k in (R.GENERAL, R.PER_MATE, R.HOST_FILING, R.HOST):
         assert routes[k]["pair_filing"] == 0
     assert all(r["flushed"] == 0 for r in routes.values())
-    for k, c in zip(knobs, ctxs):
-        assert (c.aligner_stats()["windows"] > 0) == (k != 1)
+    for k, c in zip(held_to, ctxs):
+        assert (c.aligner_stats()["windows"] > 0) == (k != R.HOST)
 
 
 def test_general_route_retry_loop():
-    """The general route with room for 4,096, then for 256 spans and candidates at first (knob 23): the loop re-reserves and
+    """The general route with room for 4,096, then for 256 spans and candidates at first (ALIGNER_FIRST_CAP): the loop re-reserves and
     runs again; from 256 the spans overflow in the first attempt and the candidates, counted over a truncated span list
     then, in the second: three attempts per mate. Same records and values as the route with its own capacities and as a context without any knob."""
     L = 100
     g, reads, indel, regions, sets = hard_case(L)
     gb, go = g.packed()
-    plain, first, second = (_ctx(gb, go, reads, 2.2 * L, 0.2 * L, 3, k) for k in (0, 4096, 256))
+    from gaml_amd.api import AlignerRoute
+    plain, first, second = (_ctx(gb, go, reads, 2.2 * L, 0.2 * L, AlignerRoute.GENERAL, k) for k in (0, 4096, 256))
     default = _ctx(gb, go, reads, 2.2 * L, 0.2 * L)  # no knob at all: whatever routes its batches take
     for i, paths in enumerate(sets):
         _same_values([c.calc_prob(paths) for c in (plain, first, second, default)])
@@ -165,7 +168,8 @@ def test_candidates_whose_seed_is_not_in_the_read_are_skipped():
     device routes skip them as the host aligner does (the reference and the oracle abort there, so no oracle here)."""
     g, reads, collide, node, sets = n_collision_case()
     gb, go = g.packed()
-    ctxs = [_ctx(gb, go, reads, 220.0, 20.0, k) for k in (0, 3, 1)]
+    from gaml_amd.api import AlignerRoute
+    ctxs = [_ctx(gb, go, reads, 220.0, 20.0, k) for k in (0, AlignerRoute.GENERAL, AlignerRoute.HOST)]
     for paths in sets:
         _same_values([c.calc_prob(paths) for c in ctxs])
     assert _same_records(ctxs) > 0

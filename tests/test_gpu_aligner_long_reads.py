@@ -19,9 +19,9 @@ def _pack_ragged(reads):
     return np.ascontiguousarray(np.concatenate(reads) if reads else np.zeros(0, np.uint8)), offs
 
 
-def _ctx(api, gb, go, reads, knob5, mean, sd):
+def _ctx(api, gb, go, reads, aligner_route, mean, sd):
     ctx = api.Context(device=0)
-    ctx.debug_set_knob(5, knob5)
+    ctx.debug_set_knob(api.Knob.ALIGNER_ROUTE, aligner_route)
     ctx.set_graph(gb, go)
     ctx.add_paired(api.paired_cfg(mean, sd), *reads)
     return ctx
@@ -40,11 +40,11 @@ def _all_windows(ctx, mate):
 
 
 def _device_equals_host_and_oracle(gb, go, reads, sets, mean, sd):
-    """A device-aligner context and its host-aligner twin (knob 5 = 1) over `sets`: equal values and floored counts, the
+    """A device-aligner context and its host-aligner twin (AlignerRoute.HOST) over `sets`: equal values and floored counts, the
     likelihood within 1e-9 of the oracle's, the device counted its windows, every window of both mates identical to the
     host aligner's, every fifth window of mate 1 identical to the oracle's. Returns the device context."""
     from gaml_amd import api
-    gpu, cpu = _ctx(api, gb, go, reads, 0, mean, sd), _ctx(api, gb, go, reads, 1, mean, sd)
+    gpu, cpu = _ctx(api, gb, go, reads, 0, mean, sd), _ctx(api, gb, go, reads, api.AlignerRoute.HOST, mean, sd)
     orc = _oracle(gb, go, reads, mean, sd)
     for paths in sets:
         a, b = gpu.calc_prob(paths), cpu.calc_prob(paths)
@@ -85,7 +85,7 @@ def test_mixed_mates_narrow_and_wide():
     reads = (*synth.pack_reads(np.ascontiguousarray(pr.mate1[:, :150])), *synth.pack_reads(pr.mate2))
     gb, go = g.packed()
     _device_equals_host_and_oracle(gb, go, reads, sets, 660.0, 60.0)
-    gpu, cpu = _ctx(api, gb, go, reads, 0, 660.0, 60.0), _ctx(api, gb, go, reads, 1, 660.0, 60.0)
+    gpu, cpu = _ctx(api, gb, go, reads, 0, 660.0, 60.0), _ctx(api, gb, go, reads, api.AlignerRoute.HOST, 660.0, 60.0)
     start, seq = synth.sa_sequence(g, 60, seed=3, threshold=400)
     for ps in [start] + seq:
         a, b = gpu.calc_prob(ps), cpu.calc_prob(ps)
@@ -111,8 +111,8 @@ def test_ragged_lengths_across_254():
 
 
 def test_three_routes_agree_at_300_bases():
-    """The paired small-batch pipeline (wide: both mates in one kernel), one small pipeline per mate (knob 5 = 4) and the
-    general route (knob 5 = 3) along an annealing-style walk: bit-equal values and records, equal window counts."""
+    """The paired small-batch pipeline (wide: both mates in one kernel), one small pipeline per mate (AlignerRoute.PER_MATE) and the
+    general route (AlignerRoute.GENERAL) along an annealing-style walk: bit-equal values and records, equal window counts."""
     from gaml_amd import api
     G, n, seed, L = 120_000, 6000, 77, 300
     genome = synth.plant_repeats(synth.make_genome(G, seed), 2, 700, seed)
@@ -120,7 +120,7 @@ def test_three_routes_agree_at_300_bases():
     pr = synth.make_paired_reads(genome, n, L, 660.0, 66.0, 0.01, seed)
     gb, go = g.packed()
     reads = (*synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
-    fast, per_mate, general = (_ctx(api, gb, go, reads, k, 660.0, 66.0) for k in (0, 4, 3))
+    fast, per_mate, general = (_ctx(api, gb, go, reads, k, 660.0, 66.0) for k in (0, api.AlignerRoute.PER_MATE, api.AlignerRoute.GENERAL))
     start, seq = synth.sa_sequence(g, 120, seed=3, threshold=400)
     for ps in [start] + seq:
         a, b, c = fast.calc_prob(ps), general.calc_prob(ps), per_mate.calc_prob(ps)
@@ -143,7 +143,7 @@ def test_the_cap_holds_at_510():
     m1[17], m2[17] = longer.mate1[0], longer.mate2[0]
     reads = (*_pack_ragged(m1), *_pack_ragged(m2))
     gb, go = g.packed()
-    gpu, cpu = _ctx(api, gb, go, reads, 0, 660.0, 60.0), _ctx(api, gb, go, reads, 1, 660.0, 60.0)
+    gpu, cpu = _ctx(api, gb, go, reads, 0, 660.0, 60.0), _ctx(api, gb, go, reads, api.AlignerRoute.HOST, 660.0, 60.0)
     for paths in sets:
         a, b = gpu.calc_prob(paths), cpu.calc_prob(paths)
         assert a[0] == b[0] and a[1].tolist() == b[1].tolist()
@@ -161,8 +161,8 @@ def test_device_aligner_is_faster_than_host_at_2x300():
     reads = (*synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
     walk = synth.genome_walk(g)
     out = {}
-    for name, knob in (("gpu", 0), ("cpu", 1)):
-        ctx = _ctx(api, gb, go, reads, knob, wl.insert_mean, wl.insert_std)
+    for name, route in (("gpu", 0), ("cpu", api.AlignerRoute.HOST)):
+        ctx = _ctx(api, gb, go, reads, route, wl.insert_mean, wl.insert_std)
         t0 = time.time()
         out[name] = (ctx.calc_prob([walk]), time.time() - t0, ctx)
     assert out["gpu"][0][0] == out["cpu"][0][0] and out["gpu"][0][1].tolist() == out["cpu"][0][1].tolist()

@@ -116,6 +116,7 @@ def test_one_pass_batch_equals_single_calls(mixed_lengths):
     against records that are loaded once. Cold (windows aligned along the way, delta lists), warm, after a table
     rebuild; chunks of 8; sets with repeated windows; an empty set. Values, floored counts and the per-read
     probabilities left behind are those of the single calls."""
+    from gaml_amd import api
     g, reads, sets, make = _paired_only(mixed_lengths)
     one, many = make(), make()
     want = [one.calc_prob(s) for s in sets]
@@ -133,7 +134,7 @@ def test_one_pass_batch_equals_single_calls(mixed_lengths):
             assert b[2] == w[2] and b[1].tolist() == w[1].tolist() and abs(b[0] - w[0]) <= 1e-13 * abs(w[0])
     # same device state on both sides now: bit for bit
     assert [b[0] for b in many.calc_prob_batch(sets[:8])] == [many.calc_prob(s)[0] for s in sets[:8]]
-    many.debug_set_knob(11, 1)  # the sequential path (one launch per set)
+    many.debug_set_knob(api.Knob.BATCH_ROUTE, api.BatchRoute.SEQUENTIAL)  # the sequential path (one launch per set)
     assert [b[0] for b in many.calc_prob_batch(sets[:8])] == [many.calc_prob(s)[0] for s in sets[:8]]
 
 
@@ -142,7 +143,7 @@ def test_candidate_batches_build_their_tables_on_the_device(two_sets):
     """Candidates of one assembly (each a single edit away from the current one): the per-set occurrence tables are
     built on the device from the resident copy + a few patched entries, and pairs whose windows no later set changed
     are finished from their first set's result. Every route must give the same bits: the device-built tables, whole
-    tables per set (knob 11 = 2), no capture (knob 11 = 3), one launch per set (knob 11 = 1), and single calls."""
+    tables per set (BatchRoute.FULL_TABLES), no capture (NO_CAPTURE), one launch per set (SEQUENTIAL), and single calls."""
     from gaml_amd import api
     G, seed = 400_000, 31
     genome = synth.make_genome(G, seed)
@@ -161,21 +162,22 @@ def test_candidate_batches_build_their_tables_on_the_device(two_sets):
         if rng.random() < 0.6:
             base = cands[int(rng.integers(0, 8))]
     ctxs = []
-    for knob in (0, 2, 3, 1, None):  # None: single calls
+    R = api.BatchRoute
+    for route in (0, R.FULL_TABLES, R.NO_CAPTURE, R.SEQUENTIAL, None):  # None: single calls
         c = api.Context(device=0)
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(250.0, 25.0), *args)
         if two_sets:  # a second library over the same assembly: its own tables, patches and launches
             c.add_paired(api.paired_cfg(400.0, 40.0, weight=0.5), *args2)
-        if knob:
-            c.debug_set_knob(11, knob)
+        if route:
+            c.debug_set_knob(api.Knob.BATCH_ROUTE, route)
         c.calc_prob(seq[-1])
-        ctxs.append((knob, c))
+        ctxs.append((route, c))
     for rnd in range(2):  # cold (windows aligned along the way), then warm
         for cands in batches:
             vals = []
-            for knob, c in ctxs:
-                if knob is None:
+            for route, c in ctxs:
+                if route is None:
                     vals.append([(c.calc_prob(s)[0], c.calc_prob(s)[1].tolist()) for s in cands])
                 else:
                     vals.append([(b[0], b[1].tolist()) for b in c.calc_prob_batch(cands)])
@@ -185,7 +187,7 @@ def test_candidate_batches_build_their_tables_on_the_device(two_sets):
                 else:
                     assert v == vals[0]
         if rnd == 0:  # the same device state everywhere: everything folded into the record tables
-            for knob, c in ctxs:
+            for route, c in ctxs:
                 c.compact_tables()
                 c.calc_prob(base)
     st = ctxs[0][1].debug_table_stats(0)

@@ -2,7 +2,7 @@
 paired_tables.hip.h) against a host check. The scenarios of tests/delta_cases.py (kept honest on the CPU by
 tests/test_delta_cases_host.py) activate as many records and windows as a launch needs: one-block launches with 1, 2, 4 and
 8 records per thread, a window cut across launches, multi-block launches with and without a window list in device memory.
-Three contexts walk each scenario -- the default, knob 22 = 1 (one-block launches only) and knob 6 = 1 (no lists: the tables
+Three contexts walk each scenario -- the default, DELTA_ONE_BLOCK (one-block launches only) and DELTA_POLICY = NO_LISTS (the tables
 rebuilt) -- next to the oracle. After every step gaml_hip_debug_delta_check compares the live tables and lists with the
 host restatement read by read, gaml_hip_debug_delta_routes says which launches ran, and the values are compared: bit for
 bit between the two list-keeping contexts (same lists, same order; only the numbering may differ), rtol 4e-16 per read
@@ -26,12 +26,13 @@ ROUTE_KEYS = ("one", "two", "four", "eight", "multi_block", "multi_block_wlist",
 
 
 def _ctx(fix, knobs=None):
+    """knobs: {name of an api.Knob: value}"""
     from gaml_amd import api
     g, pr, _ = dc.fixture(fix)
     c = api.Context(device=0)
-    c.debug_set_knob(18, 2)  # no rebuild beside the evaluations below pairs / 2 records on the lists
+    c.debug_set_knob(api.Knob.REBUILD_DIVISOR, 2)  # no rebuild beside the evaluations below pairs / 2 records on the lists
     for k, v in (knobs or {}).items():
-        c.debug_set_knob(k, v)
+        c.debug_set_knob(api.Knob[k], v)
     c.set_graph(*g.packed())
     rs = c.add_paired(api.paired_cfg(*dc.INSERT), *dc.packed_reads(pr))
     return c, rs
@@ -102,7 +103,7 @@ def _check_lists(c, rs, what):
 
 def _walk(sc_name, fix, steps, expect, oracle_steps, with_rebuilt=True):
     """the three contexts over `steps`; returns them with the per-step kind counters of the default context"""
-    knobs = [None, {22: 1}] + ([{6: 1}] if with_rebuilt else [])
+    knobs = [None, {"DELTA_ONE_BLOCK": 1}] + ([{"DELTA_POLICY": 1}] if with_rebuilt else [])  # (1: api.DeltaPolicy.NO_LISTS)
     ctxs = [_ctx(fix, k) for k in knobs]
     kinds = []
     for k, paths in enumerate(steps):
@@ -113,12 +114,12 @@ def _walk(sc_name, fix, steps, expect, oracle_steps, with_rebuilt=True):
         for i, (c, rs) in enumerate(ctxs[:2]):
             after = c.debug_delta_routes(rs)
             step = _route_step(before[i], after)
-            print(f"{what}, {'knob 22 = 1' if i else 'default'}: {after['last_records'] if k else 0} records in {after['last_windows'] if k else 0} windows, launches {step}")
+            print(f"{what}, {'DELTA_ONE_BLOCK' if i else 'default'}: {after['last_records'] if k else 0} records in {after['last_windows'] if k else 0} windows, launches {step}")
             if k > 0:
                 _assert_route(step, expect[k - 1][i], what)
                 lo, hi = expect[k - 1][2]  # the activation is what the CPU test measured for this step
                 assert lo <= after["last_records"] <= hi, (what, after)
-            r = _check_lists(c, rs, f"{what}, {'knob 22 = 1' if i else 'default'}")
+            r = _check_lists(c, rs, f"{what}, {'DELTA_ONE_BLOCK' if i else 'default'}")
             if k > 0:
                 assert r["on_lists"] > 0, (what, r)
             if i == 0:
@@ -140,7 +141,7 @@ def _batch_compact_close(sc_name, fix, ctxs, sets):
     """the last step once more through calc_prob_batch with two earlier sets (the delta body of the batch kernel, the
     wave-per-pair path over spill lists): bit-equal to single calls; then the lists folded into the tables"""
     for i, (c, rs) in enumerate(ctxs[:2]):
-        what = f"{sc_name} {'knob 22 = 1' if i else 'default'}"
+        what = f"{sc_name} {'DELTA_ONE_BLOCK' if i else 'default'}"
         batch = c.calc_prob_batch(sets)
         for (bv, bz, btl), paths in zip(batch, sets):
             sv, sz, stl = c.calc_prob(paths)
@@ -179,7 +180,7 @@ def test_scenario_routes_lists_and_values(sc):
 
 def test_large_activation_two_multi_block_launches():
     """53,149 records of 64 windows at once: two multi-block launches (49,152 records, then the rest; the window at the
-    cut in both) by default, seven one-block launches with knob 22 = 1. The oracle is called once, on the final set."""
+    cut in both) by default, seven one-block launches with DELTA_ONE_BLOCK. The oracle is called once, on the final set."""
     sc = dc.scenario("large-0-31")
     ctxs, kinds = _walk(sc.name, sc.fixture, sc.steps, _expect(sc), oracle_steps=(len(sc.steps) - 1,))
     assert kinds[-1]["on_lists"] > 20_000, kinds[-1]
@@ -217,7 +218,7 @@ def test_spill_lists_are_made_grow_and_double():
         _assert_against(vals[0], probs[0], (vals[2][0], vals[2][1], vals[2][2], probs[2]), what + " against rebuilt tables", oracle=False)
         if k % 8 == 7 or k == len(walk) - 1:
             for i, (c, rs) in enumerate(ctxs[:2]):
-                assert _check_lists(c, rs, f"{what}, {'knob 22 = 1' if i else 'default'}")["long_lists"] >= 100
+                assert _check_lists(c, rs, f"{what}, {'DELTA_ONE_BLOCK' if i else 'default'}")["long_lists"] >= 100
             _assert_against(vals[0], probs[0], _want("medium", paths), what + " against the oracle", oracle=True)
     assert moved >= 10  # (five or more activating moves, two contexts)
     _batch_compact_close("spill", "medium", ctxs, [walk[-1], steps[-1], steps[2]])
@@ -242,9 +243,9 @@ def test_multi_block_numbering_is_a_function_of_the_input(name):
     assert np.array_equal(runs[0][3], runs[1][3])
 
 
-# ---- a full store: the spill area with room for 64 long lists (knob 24), the medium fixture's repeat needs 665 at step 2
+# ---- a full store: the spill area with room for 64 long lists (DELTA_SPILL_CAP), the medium fixture's repeat needs 665 at step 2
 def _overflow_ctx():
-    c, rs = _ctx("medium", {24: 64})
+    c, rs = _ctx("medium", {"DELTA_SPILL_CAP": 64})
     steps = dc.spill_steps()
     for paths in steps[:2]:
         v, z, tl = c.calc_prob(paths)

@@ -12,10 +12,11 @@ pytestmark = pytest.mark.gpu
 
 
 def _ctx(g, pr, insert=(240.0, 24.0), knobs=None):
+    """knobs: {name of an api.Knob: value}"""
     from gaml_amd import api
     c = api.Context(device=0)
     for k, v in (knobs or {}).items():
-        c.debug_set_knob(k, v)
+        c.debug_set_knob(api.Knob[k], v)
     c.set_graph(*g.packed())
     rs = c.add_paired(api.paired_cfg(*insert), *synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
     return c, rs
@@ -31,7 +32,7 @@ def test_device_table_build_equals_the_host_restatement(n, G, repeats):
     pr = synth.make_paired_reads(genome, n, 100, 240.0, 24.0, 0.01, seed)
     walk = synth.genome_walk(g)
     for fold in (0, 1):
-        c, rs = _ctx(g, pr, knobs={16: fold})
+        c, rs = _ctx(g, pr, knobs={"KEEP_DOMINATED": fold})
         c.calc_prob([walk])
         r = c.debug_tables_check(rs)
         assert r["mismatches"] == 0 and r["pairs"] == n and r["compared"] > 4 * n, r
@@ -52,7 +53,7 @@ def test_two_builds_of_one_state_are_bit_equal():
     start, seq = synth.sa_sequence(g, 150, seed=4, threshold=400)
     vals = []
     for rep in range(2):
-        c, rs = _ctx(g, pr, knobs={14: 16, 18: 64})
+        c, rs = _ctx(g, pr, knobs={"TAKE_OVER_AFTER": 16, "REBUILD_DIVISOR": 64})
         vals.append([c.calc_prob(ps)[0] for ps in [start] + seq])
         assert c.debug_table_stats(rs)["worker_rebuilds"] >= 1
         c.close()

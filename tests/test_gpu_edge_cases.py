@@ -210,7 +210,7 @@ def test_floor_that_underflows_to_zero():
 
 def test_upload_paths_agree():
     """The per-call tables are written by the host straight into device memory (large BAR: fine-grained allocation behind
-    the PCIe BAR); knob 8 = 1 selects the pinned staging slot + hipMemcpyAsync route, knob 8 = 2 staging + copy kernel
+    the PCIe BAR); UploadRoute.MEMCPY selects the pinned staging slot + hipMemcpyAsync route, COPY_KERNEL staging + copy kernel
     (what a device without a large BAR gets). Same values bit for bit -- also for a batch."""
     from gaml_amd import api
     genome = synth.make_genome(90_000, 141)
@@ -224,10 +224,10 @@ def test_upload_paths_agree():
     [ctx.calc_prob(s) for s in sets]
     a = [ctx.calc_prob(s)[0] for s in sets]
     ab = [b[0] for b in ctx.calc_prob_batch(sets)]
-    for knob in (1, 2, 0):
-        ctx.debug_set_knob(8, knob)
-        assert [ctx.calc_prob(s)[0] for s in sets] == a, knob
-        assert [b[0] for b in ctx.calc_prob_batch(sets)] == ab, knob
+    for route in (api.UploadRoute.MEMCPY, api.UploadRoute.COPY_KERNEL, 0):
+        ctx.debug_set_knob(api.Knob.UPLOAD_ROUTE, route)
+        assert [ctx.calc_prob(s)[0] for s in sets] == a, route
+        assert [b[0] for b in ctx.calc_prob_batch(sets)] == ab, route
     assert ab == a  # one pass over the records for all sets: the same lanes, the same sums
 
 
@@ -235,7 +235,8 @@ def test_records_that_are_always_overwritten_stay_out_of_the_tables():
     """A read in the last 300 bases of a long node is aligned through the node's window and through the junction window
     that follows it; wherever both occur the node's record overwrites the junction's (graph.cc:583-592, 563-566). The
     table build leaves such junction records out (host_model.cc dominated_records): every per-pair value must be the
-    one computed with them (knob 16 = 1) and the oracle's, for path sets that use the junctions, cut them and drop them."""
+    one computed with them (Knob.KEEP_DOMINATED) and the oracle's, for path sets that use the junctions, cut them and drop them."""
+    from gaml_amd import api
     G, n, seed = 120_000, 30_000, 4242
     genome = synth.make_genome(G, seed)
     g = synth.make_graph(genome, synth.cut_lengths(G, seed, long_rng=(500, 3000)))
@@ -246,7 +247,7 @@ def test_records_that_are_always_overwritten_stay_out_of_the_tables():
     sets = [[walk], [walk[:k], walk[k:]], [walk[:k] + walk[k + 2:]], [walk[k:2 * k], walk[:k]], [walk]]
     ctx, rs, orc, ors = _both(*g.packed(), r1, r2, {}, 260.0, 26.0)
     keep, rs_k, _, _ = _both(*g.packed(), r1, r2, {}, 260.0, 26.0)
-    keep.debug_set_knob(16, 1)
+    keep.debug_set_knob(api.Knob.KEEP_DOMINATED, 1)
     for rnd in range(2):  # second round: tables rebuilt with every window of the sets on the device
         for paths in sets:
             got, kept = ctx.calc_prob(paths), keep.calc_prob(paths)
@@ -265,7 +266,7 @@ def test_records_that_are_always_overwritten_stay_out_of_the_tables():
     # node, then the nodes joined
     ctx2, rs2, orc2, ors2 = _both(*g.packed(), r1, r2, {}, 260.0, 26.0)
     keep2, rs_k2, _, _ = _both(*g.packed(), r1, r2, {}, 260.0, 26.0)
-    keep2.debug_set_knob(16, 1)
+    keep2.debug_set_knob(api.Knob.KEEP_DOMINATED, 1)
     for paths in ([[x] for x in walk], [walk[:k]] + [[x] for x in walk[k:]], [walk], [walk[:k], walk[k:]], [[x] for x in walk]):
         got, kept = ctx2.calc_prob(paths), keep2.calc_prob(paths)
         assert np.array_equal(ctx2.read_probs(rs2), keep2.read_probs(rs_k2))
@@ -279,10 +280,11 @@ def test_records_that_are_always_overwritten_stay_out_of_the_tables():
 def test_static_memo_indices_change_no_value(ragged):
     """A compact-class pair whose two records sit in the same window gets its memo index when the tables are built
     (host_model.cc build_pair_tables: orientation rule and insert distance, graph.cc:1864-1882, do not depend on where the
-    window sits); the scoring launch then only asks the occurrence tables WHETHER the pair scores. Knob 19 = 1 resolves
+    window sits); the scoring launch then only asks the occurrence tables WHETHER the pair scores. Knob.NO_STATIC_INDEX resolves
     every pair per call instead. Same per-read probabilities bit for bit -- over path sets that use, cut, drop, invert and
     repeat the windows (general path), for one and for several read-length combinations, single calls and batches -- and
     both agree with the oracle."""
+    from gaml_amd import api
     G, n, seed = 150_000, 36_000, 777
     rng = np.random.default_rng(seed)
     genome = synth.make_genome(G, seed)
@@ -302,7 +304,7 @@ def test_static_memo_indices_change_no_value(ragged):
             [walk[:k] + [-35] + walk[k:]], [walk, walk[k:2 * k]], [walk[:k] + walk[:k]], [], [walk]]
     ctx, rs, orc, ors = _both(*g.packed(), r1, r2, {}, 260.0, 26.0)
     dyn, rs_d, _, _ = _both(*g.packed(), r1, r2, {}, 260.0, 26.0)
-    dyn.debug_set_knob(19, 1)
+    dyn.debug_set_knob(api.Knob.NO_STATIC_INDEX, 1)
     for rnd in range(2):  # second round: tables rebuilt with every window of the sets on the device
         for paths in sets:
             got, want = ctx.calc_prob(paths), dyn.calc_prob(paths)

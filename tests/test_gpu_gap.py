@@ -34,15 +34,15 @@ class Case:
         self.g, self.m1, self.m2 = g, list(m1), list(m2)
         self.walk = synth.genome_walk(g)
 
-    def make(self, single=None, penalty=0.0, devices=None, knob18=False):
+    def make(self, single=None, penalty=0.0, devices=None, gap_fallback=False):
         from gaml_amd import api
         c = api.Context(device=0) if devices is None else api.Context(devices=devices)
         c.set_graph(*self.g.packed())
         c.add_paired(api.paired_cfg(go.INSERT_MEAN, go.INSERT_STD, penalty_constant=penalty), *_pack(self.m1), *_pack(self.m2))
         if single is not None:
             c.add_single(api.single_cfg(), *synth.pack_reads(single))
-        if knob18:
-            c.debug_set_knob(18, 1)
+        if gap_fallback:
+            c.debug_set_knob(api.Knob.GAP_FALLBACK, 1)
         return c
 
     def oracle(self):
@@ -181,7 +181,7 @@ def test_profile_against_the_oracle_with_repeats(repeats):
 
 def test_routes(plain):
     """A context of paired sets scores every length on the device route; a single-end set beside the paired one, a
-    coverage penalty, knob 18 and a multi-device context report the fallback. Same values whatever the route."""
+    coverage penalty, Knob.GAP_FALLBACK and a multi-device context report the fallback. Same values whatever the route."""
     paths, path_id, gap_pos, lens = _profile_cases(plain.walk)["nine lengths"]
     sets = [go.with_length(paths, path_id, gap_pos, l) for l in lens]
     dev = plain.make()
@@ -199,7 +199,7 @@ def test_routes(plain):
         return length, trace
 
     want_len, want_trace = dev.fix_gap_length(paths, path_id, gap_pos)
-    got = fallback(plain.make(knob18=True), ref, 1e-13)
+    got = fallback(plain.make(gap_fallback=True), ref, 1e-13)
     assert got[0] == want_len and [l for l, _ in got[1]] == [l for l, _ in want_trace]
     got = fallback(plain.make(devices=[0, 0]), ref, 1e-13)
     assert got[0] == want_len and [l for l, _ in got[1]] == [l for l, _ in want_trace]

@@ -1,5 +1,5 @@
 """Occurrence tables of whole-set calls built on the device (gaml_amd/csrc/occ_device.hip.h): the route against the host
-route (knob 17 = 1) in a second context fed the same calls -- values, zeros, total length and per-read probabilities bit-equal
+route (Knob.NO_OCC_DEVICE) in a second context fed the same calls -- values, zeros, total length and per-read probabilities bit-equal
 -- the device tables against the host image entry by entry, the fallback when two paths share a window, and the
 transitions to the routes that need the host images (incremental calls, batches, table rebuilds)."""
 import numpy as np
@@ -27,11 +27,11 @@ def _pair(name, with_oracle=False):
     gb, go = g.packed()
     r1, r2 = synth.pack_reads(pr.mate1), synth.pack_reads(pr.mate2)
     ctxs = []
-    for knob17 in (0, 1):
+    for no_occ_device in (0, 1):
         c = api.Context(device=0)
         c.set_graph(gb, go)
         c.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std), *r1, *r2)
-        c.debug_set_knob(17, knob17)
+        c.debug_set_knob(api.Knob.NO_OCC_DEVICE, no_occ_device)
         ctxs.append(c)
     orc = None
     if with_oracle:

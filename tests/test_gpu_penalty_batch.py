@@ -107,12 +107,13 @@ def _oracle(variant, two=False):
     return out
 
 
-def _ctx(variant, two=None, knob11=0):
-    """two: None one library; True a second, penalised one beside it; False a second one without penalty"""
+def _ctx(variant, two=None, batch_route=None):
+    """two: None one library; True a second, penalised one beside it; False a second one without penalty; batch_route: the
+    name of an api.BatchRoute"""
     from gaml_amd import api
     c = api.Context(device=0)
-    if knob11:
-        c.debug_set_knob(11, knob11)
+    if batch_route:
+        c.debug_set_knob(api.Knob.BATCH_ROUTE, api.BatchRoute[batch_route])
     c.set_graph(*_graph()[1].packed())
     c.add_paired(api.paired_cfg(240.0, 24.0, penalty_constant=PENALTY), *_reads(variant))
     if two is not None:
@@ -165,7 +166,7 @@ def test_batch_takes_the_one_pass_routes():
     launches = c.kernel_stats()["launches"]
     print("scoring launches of one 8-set batch:", launches)
     assert 1 <= launches <= 2  # (one read set: the two halves of the batch)
-    s = _ctx("one", knob11=1)  # the sequential path: one call per path set
+    s = _ctx("one", batch_route="SEQUENTIAL")  # the sequential path: one call per path set
     s.calc_prob(base)
     s.calc_prob_batch(fam["cands"])
     s.calc_prob_batch(fam["unrel"])
@@ -207,12 +208,13 @@ def test_batch_equals_single_calls(variant):
     # warm: every chunk (1 + 1 + 1 + 2) takes a one-pass route, some of them from patches
     assert sum(chunks[1]) - sum(chunks[0]) == 5 and chunks[1][0] > chunks[0][0], chunks
     # one context, the same device state on both sides: every route gives the single calls' bits
-    for knob in (0, 2, 3, 1):
-        many_ctx.debug_set_knob(11, knob)
+    from gaml_amd.api import BatchRoute, Knob
+    for route in (0, BatchRoute.FULL_TABLES, BatchRoute.NO_CAPTURE, BatchRoute.SEQUENTIAL):
+        many_ctx.debug_set_knob(Knob.BATCH_ROUTE, route)
         for name, sets in order[:3]:
             got = _batch(many_ctx, sets)
-            _same(got, [_call(many_ctx, s) for s in sets], 0, ("knob 11", knob, name))
-    many_ctx.debug_set_knob(11, 0)
+            _same(got, [_call(many_ctx, s) for s in sets], 0, ("BATCH_ROUTE", route, name))
+    many_ctx.debug_set_knob(Knob.BATCH_ROUTE, 0)
     # what a batch leaves behind is the last set's
     got = _batch(many_ctx, fam["cands"])
     assert many_ctx.bad_bases(0) == got[-1][3][0]
@@ -276,7 +278,7 @@ def test_gap_search_through_the_fallback():
     gap_set, gap_path, gap_pos = _graph()[4]
     twin = [y ^ 1 for y in reversed(gap_set[(gap_path + 1) % len(gap_set)]) if y >= 0]
     full = gap_set + [twin]
-    dev, seq_ctx = _ctx("one"), _ctx("one", knob11=1)
+    dev, seq_ctx = _ctx("one"), _ctx("one", batch_route="SEQUENTIAL")
     res = []
     for c in (dev, seq_ctx):  # identical call sequences
         c.calc_prob(full)

@@ -5,8 +5,8 @@ the general form. Now it plans incrementally, patches the resident copy of the t
 whole per call) and marks coverage from the memo / streamed-value bodies of the scoring kernel (its COV instantiation).
 Over an annealing-style walk of 121 path sets, for pairs of one length combination and for trimmed mates (several
 combinations: the length-code tables):
-  * four contexts -- default, knob 12 = 1 (every set planned from scratch), knob 13 = 1 (whole tables through the ring),
-    knob 21 = 1 (the compact class in its general form, marking through the same slot layout) -- agree bit for bit, and the default one really takes the new route (incremental planning, static pairs, bytes written);
+  * four contexts -- default, PLAN_WHOLE_SET (every set planned from scratch), NO_RESIDENT_TABLES (whole tables through the
+    ring), NO_COV_INSTANCE (the compact class in its general form, marking through the same slot layout) -- agree bit for bit, and the default one really takes the new route (incremental planning, static pairs, bytes written);
   * the default context agrees with the oracle at every step (bad_bases and floored counts exactly);
   * calls of other kinds in between -- stream-ordered (ring route), calc_partials, a table fold, a batch, a gap-length
     search -- leave the resident copy and the layout usable: a twin that only makes blocking calls gets the same results;
@@ -58,11 +58,12 @@ def _case(trimmed):
 
 
 def _ctx(case, knob=None):
+    """knob: the name of an api.Knob to set to 1"""
     from gaml_amd import api
     g, reads = case[0], case[1]
     c = api.Context(device=0)
     if knob is not None:
-        c.debug_set_knob(knob, 1)
+        c.debug_set_knob(api.Knob[knob], 1)
     c.set_graph(*g.packed())
     c.add_paired(api.paired_cfg(240.0, 24.0, penalty_constant=PENALTY), *reads)
     return c
@@ -89,7 +90,7 @@ def test_oracle_inputs_exercise_the_penalty(trimmed):
 def test_three_routes_agree_bit_for_bit(trimmed):
     case = _case(trimmed)
     sets = case[2]
-    dflt, scratch, ring, general = _ctx(case), _ctx(case, 12), _ctx(case, 13), _ctx(case, 21)
+    dflt, scratch, ring, general = _ctx(case), _ctx(case, "PLAN_WHOLE_SET"), _ctx(case, "NO_RESIDENT_TABLES"), _ctx(case, "NO_COV_INSTANCE")
     incremental = 0
     bytes_dflt = bytes_ring = 0.0
     for k, ps in enumerate(sets):
@@ -109,7 +110,7 @@ def test_three_routes_agree_bit_for_bit(trimmed):
         if inc:
             bytes_dflt += dflt.last_phases()[6]
             bytes_ring += ring.last_phases()[6]
-    print("incremental steps", incremental, "bytes written on them: default", bytes_dflt, "knob 13", bytes_ring)
+    print("incremental steps", incremental, "bytes written on them: default", bytes_dflt, "NO_RESIDENT_TABLES", bytes_ring)
     assert incremental > len(sets) // 2
     assert dflt.table_stats(0)["static_index_pairs"] > 0
     # a patch of the resident copy + the coverage layout against whole tables through the ring

@@ -66,7 +66,7 @@ def test_delta_list_equals_full_rebuild():
     ctxs = []
     for no_delta in (0, 1):
         c = api.Context(device=0)
-        c.debug_set_knob(6, no_delta)
+        c.debug_set_knob(api.Knob.DELTA_POLICY, api.DeltaPolicy.NO_LISTS if no_delta else 0)
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(240.0, 24.0), *synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
         ctxs.append(c)
@@ -86,8 +86,8 @@ def test_delta_list_equals_full_rebuild():
 
 def test_incremental_planning_and_resident_tables_change_no_bit():
     """Three contexts walk the same annealing-style sequence: (a) the default -- paths diffed against the previous call,
-    the resident device copy of the occurrence tables patched in place; (b) every set planned from scratch (knob 12);
-    (c) whole tables through the ring for every call (knob 13). Values, floored counts and per-read probabilities are
+    the resident device copy of the occurrence tables patched in place; (b) every set planned from scratch (PLAN_WHOLE_SET);
+    (c) whole tables through the ring for every call (NO_RESIDENT_TABLES). Values, floored counts and per-read probabilities are
     equal bit for bit at every step (the tables describe the same occurrences; slots and ranks only ever enter through
     equality / order within one path)."""
     from gaml_amd import api
@@ -96,11 +96,11 @@ def test_incremental_planning_and_resident_tables_change_no_bit():
     g = synth.make_graph(genome, synth.cut_lengths(G, seed, long_rng=(600, 4000), short_rng=(25, 330)))
     pr = synth.make_paired_reads(genome, n, 100, 240.0, 24.0, 0.01, seed)
     ctxs = []
-    for knob in (None, 12, 13):
+    for knob in (None, api.Knob.PLAN_WHOLE_SET, api.Knob.NO_RESIDENT_TABLES):
         c = api.Context(device=0)
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(240.0, 24.0), *synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
-        if knob:
+        if knob is not None:
             c.debug_set_knob(knob, 1)
         ctxs.append(c)
     start, seq = synth.sa_sequence(g, 300, seed=5, threshold=400)
@@ -125,7 +125,8 @@ def test_incremental_planning_and_resident_tables_change_no_bit():
 def test_rebuild_on_the_worker_thread_takes_over_mid_walk():
     """When the delta lists pass pairs / 8 the record tables are rebuilt by a worker thread from a private copy while
     evaluations go on; a later call swaps the new tables in and re-bases the pairs touched since the snapshot. Against
-    a context that rebuilds on the calling thread (knob 14) and one that never uses delta lists (knob 6 = 1): same
+    a context that rebuilds on the calling thread (REBUILD_ON_CALLER) and one that never uses delta lists (DELTA_POLICY =
+    NO_LISTS): same
     floored counts, values and per-read probabilities within re-association noise."""
     from gaml_amd import api
     G, n, seed = 200_000, 36_000, 23
@@ -137,7 +138,8 @@ def test_rebuild_on_the_worker_thread_takes_over_mid_walk():
     # again, but slowed down: its worker is done long before the take-over, so the lists that go with the new tables are
     # prepared in other slices than the first context's -- and every value must still be equal bit for bit (the point
     # of a take-over at a fixed evaluation count)
-    for knobs in ({14: 40}, {14: 1}, {6: 1}, {14: 40}):
+    K = api.Knob
+    for knobs in ({K.TAKE_OVER_AFTER: 40}, {K.REBUILD_ON_CALLER: 1}, {K.DELTA_POLICY: api.DeltaPolicy.NO_LISTS}, {K.TAKE_OVER_AFTER: 40}):
         c = api.Context(device=0)
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(240.0, 24.0), *synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
@@ -170,8 +172,8 @@ def test_rebuild_on_the_worker_thread_takes_over_mid_walk():
 
 def test_worker_take_overs_at_the_large_table_scale_against_the_oracle():
     """The rebuild machinery at the scale where build_pair_tables takes its multi-threaded branch (>= 2^16 pairs): 90,000
-    pairs, tables rebuilt when the delta lists pass pairs / 64 (knob 18) and taken over 24 evaluations after the worker
-    started (knob 14), so that several take-overs -- snapshot in slices, second delta store, re-basing of what was
+    pairs, tables rebuilt when the delta lists pass pairs / 64 (REBUILD_DIVISOR) and taken over 24 evaluations after the worker
+    started (TAKE_OVER_AFTER), so that several take-overs -- snapshot in slices, second delta store, re-basing of what was
     activated meanwhile, windows retired while a snapshot is copied -- happen within a few hundred annealing steps.
     Value, floored count and per-read probabilities against the ORACLE (fresh scoring state) at every step."""
     import oracle_py as op
@@ -184,8 +186,8 @@ def test_worker_take_overs_at_the_large_table_scale_against_the_oracle():
     ctx = api.Context(device=0)
     ctx.set_graph(*g.packed())
     rs = ctx.add_paired(api.paired_cfg(240.0, 24.0), *r1, *r2)
-    ctx.debug_set_knob(14, 24)
-    ctx.debug_set_knob(18, 64)
+    ctx.debug_set_knob(api.Knob.TAKE_OVER_AFTER, 24)
+    ctx.debug_set_knob(api.Knob.REBUILD_DIVISOR, 64)
     orc = op.Oracle()
     orc.set_graph(*g.packed())
     ors = orc.add_paired(*r1, *r2, 0.01, op.paired_cfg(240.0, 24.0))
@@ -244,15 +246,15 @@ def test_destroy_and_compact_while_a_rebuild_is_in_flight(phase):
         assert st["dirty_pairs"] > 4096 and st["worker_rebuilds"] == before["worker_rebuilds"]  # decided, not taken over
         return v
 
-    ref = make({14: 1})  # rebuilds on the calling thread only
+    ref = make({api.Knob.REBUILD_ON_CALLER: 1})  # rebuilds on the calling thread only
     want = [ref.calc_prob(p) for p in ([[x] for x in walk], [walk], [walk[:k], walk[k:]], [walk])]
     # (1) destroy in flight, several times (the worker is at a different point each time)
     for _ in range(3):
-        c = make({14: 100000})
+        c = make({api.Knob.TAKE_OVER_AFTER: 100000})
         into_flight(c)
         c.close()
     # (2) compact in flight: the calling thread joins the worker, discards or uses its tables, rebuilds -- values unchanged
-    c = make({14: 100000})
+    c = make({api.Knob.TAKE_OVER_AFTER: 100000})
     v = into_flight(c)
     assert v[1].tolist() == want[1][1].tolist() and abs(v[0] - want[1][0]) <= 1e-12 * abs(want[1][0])
     c.compact_tables()

@@ -2,7 +2,7 @@
 one only looks at the paths in between. After every step of a long annealing-style walk of path sets
   * the occurrence TABLES (the host image the device copy mirrors) describe exactly the occurrences the planner's memos
     list for the set, and
-  * a second context that plans every set from scratch (knob 12) has the same occurrences, windows and records."""
+  * a second context that plans every set from scratch (PLAN_WHOLE_SET) has the same occurrences, windows and records."""
 import numpy as np
 import pytest
 
@@ -40,7 +40,7 @@ def test_incremental_tables_equal_planning_from_scratch(built, seed):
     pr = synth.make_paired_reads(genome, n, 100, 240.0, 24.0, 0.01, seed)
     reads = (*synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
     inc, ref = api.Context(device=-1), api.Context(device=-1)
-    ref.debug_set_knob(12, 1)  # every set planned from scratch
+    ref.debug_set_knob(api.Knob.PLAN_WHOLE_SET, 1)  # every set planned from scratch
     for c in (inc, ref):
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(240.0, 24.0), *reads)
@@ -86,7 +86,7 @@ def test_candidates_of_one_assembly_stay_incremental(built):
     pr = synth.make_paired_reads(genome, n, 100, 240.0, 24.0, 0.01, seed)
     reads = (*synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
     inc, ref = api.Context(device=-1), api.Context(device=-1)
-    ref.debug_set_knob(12, 1)
+    ref.debug_set_knob(api.Knob.PLAN_WHOLE_SET, 1)
     for c in (inc, ref):
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(240.0, 24.0), *reads)

@@ -1,7 +1,7 @@
 """Incremental planning of a read set WITH a coverage penalty, on the host (no GPU). The penalty's bitmap layout used to
 force whole-set planning; now the table entries carry path slots and the layout maps a slot to its bit region. After
 every step of an annealing-style walk
-  * the occurrence tables equal those of a context that plans every set from scratch (knob 12), and
+  * the occurrence tables equal those of a context that plans every set from scratch (PLAN_WHOLE_SET), and
   * the coverage layout of the call (debug_cov_layout) gives every path a region of its own that holds it, names the
     same region by slot and by position, and lists the contig starts the sweep needs."""
 import numpy as np
@@ -55,7 +55,7 @@ def test_penalised_set_plans_incrementally_with_a_slot_layout(built):
     pr = synth.make_paired_reads(genome, n, 100, 240.0, 24.0, 0.01, seed)
     reads = (*synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
     inc, ref = api.Context(device=-1), api.Context(device=-1)
-    ref.debug_set_knob(12, 1)  # every set planned from scratch
+    ref.debug_set_knob(api.Knob.PLAN_WHOLE_SET, 1)  # every set planned from scratch
     for c in (inc, ref):
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(240.0, 24.0, penalty_constant=0.0002), *reads)

@@ -15,7 +15,7 @@ for rnd in range(2):
     ctx = api.Context(device=0)
     ctx.set_graph(*g.packed())
     t = time.perf_counter(); rs = ctx.add_paired(api.paired_cfg(300.0, 30.0), *reads); t_add = time.perf_counter() - t
-    ctx.debug_set_knob(9, 1)
+    ctx.debug_set_knob(api.Knob.ALIGNER_TIMED, 1)
     t = time.perf_counter(); ctx.calc_prob(start); dt = time.perf_counter() - t
     ph = ctx.debug_profile()
     print(f"context {rnd}: add_paired {t_add * 1e3:.1f} ms; cold call {dt * 1e3:.1f} ms; phases us [pass1, tables_host, align (in pass1), write, sync(tables), launch, bytes, wait]:", np.round(ph, 0), flush=True)

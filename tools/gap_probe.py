@@ -3,7 +3,7 @@
   a  the search restated in Python (tests/gap_oracle.py) driving blocking gaml_hip_calc_prob calls through ctypes, one per
      evaluation, on a prebuilt flat path set whose gap entry is rewritten in place (what a caller could do before
      gaml_hip_fix_gap_length existed)
-  b  gaml_hip_fix_gap_length on a context with knob 18 = 1: the fallback route, one batch call per step of the search
+  b  gaml_hip_fix_gap_length on a context with Knob.GAP_FALLBACK: the fallback route, one batch call per step of the search
   c  gaml_hip_fix_gap_length on the device route: passes of up to 8 lengths, tables derived on the device
 
 The path set is the genome walk cut into contigs of `--contig` nodes; a site replaces one inner node of a contig by a gap
@@ -96,7 +96,7 @@ def main():
         ctx.set_graph(*g.packed())
         ctx.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std), *r1, *r2)
         if name == "b":
-            ctx.debug_set_knob(18, 1)
+            ctx.debug_set_knob(api.Knob.GAP_FALLBACK, 1)
         ways.append(Way(name, ctx))
     # one flat path set per site (the node at the site replaced by the gap), built before anything is timed
     fps = []

@@ -1,6 +1,6 @@
 """Where does a wave of the scoring kernel spend its time?  Ablation 8 stamps the wall clock (10 ns units) at the
 stage boundaries of every wave; this prints per class the distribution of each stage, relative to the first wave's
-entry.  python tools/kernel_timeline.py [cfg3]"""
+entry.  python tools/kernel_timeline.py [cfg3] ["{NO_STATIC_INDEX: 1, 10: 128}"]  (knobs set first, by api.Knob name or number)"""
 import os, sys
 os.environ.setdefault("GAML_HIP_FLAVOUR", "dev")  # tools look inside the library: the development build
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,9 +18,9 @@ variants = [api.FlatPaths(v) for v in bench.path_variants(synth.genome_walk(g))]
 [ctx.calc_prob(v) for v in variants]
 ctx.compact_tables()
 [ctx.calc_prob(v) for v in variants]
-for k, v in eval(sys.argv[2]).items() if len(sys.argv) > 2 else []:
+for k, v in eval(sys.argv[2], dict(api.Knob.__members__)).items() if len(sys.argv) > 2 else []:
     ctx.debug_set_knob(k, v)
-ctx.debug_set_knob(3, 8)
+ctx.debug_set_knob(api.Knob.TIMELINE, 8)
 names = ["entry", "tables->LDS", "records in", "occurrences in", "memo in", "stores out", "block reduced"]
 for rep in range(3):
     for i in range(8):

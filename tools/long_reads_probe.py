@@ -1,5 +1,5 @@
 """The 2x300 workload (synth.WORKLOADS["cfg2x300"]: reads above 254 bases, the aligner's wide kernels): the cold first call
-with the device aligner and with the host aligner (knob 5 = 1), the small batches along the annealing pattern, the aligner's
+with the device aligner and with the host aligner (ALIGNER_ROUTE = HOST), the small batches along the annealing pattern, the aligner's
 stages -- one JSON line.  python tools/long_reads_probe.py [--iters N] [--no-host]"""
 import argparse, json, os, sys, time
 os.environ.setdefault("GAML_HIP_FLAVOUR", "dev")  # tools look inside the library: the development build
@@ -22,11 +22,11 @@ start, seq = synth.sa_sequence(g, args.iters)
 flat = [api.FlatPaths(p) for p in seq]
 
 
-def cold(knob5):
+def cold(aligner_route):
     ctx = api.Context(device=0)
     ctx.set_graph(*g.packed())
     ctx.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std), *reads)
-    ctx.debug_set_knob(5, knob5)
+    ctx.debug_set_knob(api.Knob.ALIGNER_ROUTE, aligner_route)
     t = time.perf_counter(); value = ctx.calc_prob(start)[0]; dt = time.perf_counter() - t
     return ctx, value, dt
 
@@ -56,7 +56,7 @@ out["stages_us_total"] = {k: round(float(v), 1) for k, v in sg2.items() if k != 
 v_end = ctx.calc_prob(seq[-1])[0] if seq else v_dev
 ctx.close()
 if not args.no_host:
-    host, v_host, t_host = cold(1)
+    host, v_host, t_host = cold(api.AlignerRoute.HOST)
     hs = host.aligner_stats()
     per_h = []
     for f in flat:

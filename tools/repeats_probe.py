@@ -15,7 +15,7 @@ def late_walk(iters):
     pr = synth.make_paired_reads(genome, wl.n_pairs, wl.read_len, wl.insert_mean, wl.insert_std, wl.err, wl.seed)
     ctx = api.Context(device=0)
     for kv in filter(None, os.environ.get("KNOBS", "").split(",")):
-        ctx.debug_set_knob(*map(int, kv.split("=")))
+        ctx.debug_set_knob(*api.parse_knob(kv))
     ctx.set_graph(*g.packed())
     rs = ctx.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std), *synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
     start, seq = synth.sa_sequence(g, iters)
@@ -46,8 +46,8 @@ pr = synth.make_paired_reads(genome, wl.n_pairs, wl.read_len, wl.insert_mean, wl
 gb, go = g.packed()
 r1, r2 = synth.pack_reads(pr.mate1), synth.pack_reads(pr.mate2)
 ctx = api.Context(device=0)
-for kv in filter(None, os.environ.get("KNOBS", "").split(",")):  # e.g. KNOBS=10=128
-    ctx.debug_set_knob(*map(int, kv.split("=")))
+for kv in filter(None, os.environ.get("KNOBS", "").split(",")):  # e.g. KNOBS=GRID_CAP_CLASS1=128 (or by number: 10=128)
+    ctx.debug_set_knob(*api.parse_knob(kv))
 ctx.set_graph(gb, go)
 rs = ctx.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std), *r1, *r2)
 walk = synth.genome_walk(g)

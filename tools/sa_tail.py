@@ -1,4 +1,4 @@
-"""Tail of the annealing pattern at cfg3: per-call times with / without the quiet-spell table fold (knob 6 = 2), where
+"""Tail of the annealing pattern at cfg3: per-call times with / without the quiet-spell table fold (DELTA_POLICY = NO_QUIET_REBUILD), where
 the slow calls come from, aligner stage breakdown.  python tools/sa_tail.py"""
 import os, sys, time
 os.environ.setdefault("GAML_HIP_FLAVOUR", "dev")  # tools look inside the library: the development build
@@ -12,12 +12,12 @@ pr = synth.make_paired_reads(genome, wl.n_pairs, wl.read_len, wl.insert_mean, wl
 reads = (*synth.pack_reads(pr.mate1), *synth.pack_reads(pr.mate2))
 start, seq = synth.sa_sequence(g, int(os.environ.get("SA_ITERS", "1000")))
 flat = [api.FlatPaths(p) for p in seq]
-for knob6 in (0,):
+for policy in (0,):
     ctx = api.Context(device=0)
     ctx.set_graph(*g.packed())
     rs = ctx.add_paired(api.paired_cfg(300.0, 30.0), *reads)
-    ctx.debug_set_knob(6, knob6)
-    ctx.debug_set_knob(9, 1)
+    ctx.debug_set_knob(api.Knob.DELTA_POLICY, policy)
+    ctx.debug_set_knob(api.Knob.ALIGNER_TIMED, 1)
     if os.environ.get("SA_WARM"):  # as bench.py: the context has scored the 8 rotating path sets of the headline (tables built over THEIR windows) first
         import bench
         variants = [api.FlatPaths(v) for v in bench.path_variants(synth.genome_walk(g))]
@@ -34,7 +34,7 @@ for knob6 in (0,):
         a = ctx.aligner_stats()["windows"]; kinds.append(a - a_prev); a_prev = a
     per = np.array(per); kinds = np.array(kinds); prof = np.array(prof)
     al = kinds > 0
-    print(f"knob6={knob6}: total {per.sum() / 1e3:.1f} ms, median {np.median(per):.1f}, p90 {np.percentile(per, 90):.1f}, p99 {np.percentile(per, 99):.1f}, max {per.max():.0f} us; "
+    print(f"DELTA_POLICY={policy}: total {per.sum() / 1e3:.1f} ms, median {np.median(per):.1f}, p90 {np.percentile(per, 90):.1f}, p99 {np.percentile(per, 99):.1f}, max {per.max():.0f} us; "
           f"calls that aligned windows: {al.sum()} (median {np.median(per[al]):.0f} us, p90 {np.percentile(per[al], 90):.0f}); others median {np.median(per[~al]):.1f} p99 {np.percentile(per[~al], 99):.1f}")
     print("   aligning calls, median phases [pass1, tables_host, align (in pass1), write, sync(delta), launch, bytes, wait]:", np.round(np.median(prof[al], axis=0), 1))
     print("   other calls,    median phases:", np.round(np.median(prof[~al], axis=0), 1))

@@ -34,9 +34,10 @@ for seed in range(200, 200 + n_seeds):
     ctx = api.Context(device=0)
     # the table machinery at sizes where it would otherwise never run: rebuilds when the delta lists pass pairs / d, taking over
     # k evaluations after their start (1: on the calling stream), delta maintenance by one-block / multi-block launches
-    knobs = {18: int(rng.choice([0, 16, 64])), 14: int(rng.choice([0, 1, 8, 24])), 22: int(rng.choice([0, 1]))}
+    divisor, take_over, one_block = int(rng.choice([0, 16, 64])), int(rng.choice([0, 1, 8, 24])), int(rng.choice([0, 1]))
+    knobs = {"REBUILD_DIVISOR": divisor, "REBUILD_ON_CALLER": int(take_over == 1), "TAKE_OVER_AFTER": take_over if take_over > 1 else 0, "DELTA_ONE_BLOCK": one_block}
     for k, v in knobs.items():
-        ctx.debug_set_knob(k, v)
+        ctx.debug_set_knob(api.Knob[k], v)
     ctx.set_graph(*g.packed())
     rs = ctx.add_paired(api.paired_cfg(mean, mean / 10, penalty_constant=penalty), *args)
     orc = op.Oracle()
