@@ -12,7 +12,9 @@
 //
 //   gap_tables_kernel     region g of an arena slot := the resident tables, those shift words + (lens[g] - base)
 //   gap_profile_device    plan the set once with the base length, then per pass of up to kMaxSets lengths: thresholds
-//                         through the BAR, gap_tables_kernel, paired_score_multi_kernel (launch_paired_multi, unchanged)
+//                         through the BAR, gap_tables_kernel, paired_score_multi_kernel (launch_paired_multi, unchanged);
+//                         scope, wait and results of a pass are the batch routes' (MultiPass, multi_wait, multi_collect:
+//                         paired_batch.hip.h), the copy geometry theirs too (paired_tab_geometry)
 //   gap_profile_fallback  the same lengths as path sets of gaml_hip_calc_prob_batch / collective gaml_hip_calc_prob calls
 //   gaml_hip_fix_gap_length  the search, its evaluations taken from passes of lengths chosen before they are needed
 #pragma once
@@ -124,8 +126,8 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     int path_slot = 0, first_rank[2] = {0, 0};
   };
   std::vector<PerSet> per(nps);
-  c->host_results = true;
-  struct Reset { gaml_hip_ctx* c; ~Reset() { c->host_results = false; c->pending_open = false; } } reset{c};
+  const int chunk = std::min<int32_t>(kMaxSets, n_lens);
+  MultiPass pass(c, chunk);  // (every pass of `chunk` lengths goes out in one launch: nothing to plan beside it)
   for (size_t i = 0; i < nps; i++) { if (int e = prepare_paired_tables(c, *c->paireds[i])) return e; }
   int64_t pending = 0;
   if (int e = eval_begin(c, c->gap_flat.data(), c->gap_offs.data(), n_paths, &pending)) return e;
@@ -134,7 +136,6 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
   // (an occurrence's shift is where its node starts), every one behind it at or after
   int64_t gap_from = 0;
   for (int64_t q = c->gap_offs[path_id]; q < c->gap_offs[path_id] + gap_pos; q++) gap_from += c->gap_flat[q] < 0 ? -(int64_t)c->gap_flat[q] : c->g.len(c->gap_flat[q]);
-  const int chunk = std::min<int32_t>(kMaxSets, n_lens);
   for (size_t i = 0; i < nps; i++) {
     PairedSet& ps = *c->paireds[i];
     PerSet& r = per[i];
@@ -143,10 +144,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     if (int e = paired_sync_tables(c, ps, st)) return e;
     PairedSet::Persist& P = ps.persist;
     // the resident copy follows the images: now the set with the base length
-    if (!P.valid || ps.image[0].changed_all || ps.image[1].changed_all || !ps.image[0].changed.empty() || !ps.image[1].changed.empty() ||
-        ps.image[0].lists_changed || ps.image[1].lists_changed) {
-      if (int e = paired_persist_update(c, ps, (double)(2 * (tl0 == 0 ? 1 : tl0)), st)) return e;
-    }
+    if (paired_persist_stale(ps)) { if (int e = paired_persist_update(c, ps, (double)(2 * (tl0 == 0 ? 1 : tl0)), st)) return e; }
     if ((size_t)path_id >= ps.planner.slots().size()) return fail(c, GAML_HIP_ESTATE, "gap profile: the planner does not hold the path set");
     r.path_slot = ps.planner.slots()[(size_t)path_id];
     const PathMemo& pm = ps.planner.memo(ps.planner.ids()[(size_t)path_id]);
@@ -159,10 +157,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
       r.chg_bytes[mt] = align16(r.bw[mt]);
     }
     r.stride = align16(P.bytes);
-    r.L.tfloor_off = P.off_tfloor;
-    r.L.l0 = OccLayout{P.off_occ[0], P.off_lo[0], P.off_m[0], P.off_lo[1] /* unused */};
-    r.L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.bytes};
-    r.L.sb_off = r.L.pb_off = r.L.so_off = r.L.st_off = 0; r.L.total = P.bytes;
+    r.L = paired_persist_layout(P);
     r.Ls.assign((size_t)chunk, r.L);
     { const PairedPrep one = r.prep[0]; r.prep.assign((size_t)chunk, one); }  // every length: the same windows, lists and records
     if (int e = arena_acquire(c, ps.arena, r.stride * (size_t)chunk + r.chg_bytes[0] + r.chg_bytes[1], st, &r.slot, &r.wp)) return e;
@@ -177,26 +172,17 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     for (size_t i = 0; i < nps; i++) {
       PairedSet& ps = *c->paireds[i];
       PerSet& r = per[i];
-      const PairedSet::Persist& P = ps.persist;
-      for (int k = 0; k < n; k++) paired_pack_thresholds(ps, r.L, (double)(2 * (tls[k] == 0 ? 1 : tls[k])), r.wp + (size_t)k * r.stride);
+      for (int k = 0; k < n; k++) paired_pack_thresholds(ps, r.L.tfloor_off, (double)(2 * (tls[k] == 0 ? 1 : tls[k])), r.wp + (size_t)k * r.stride);
       if (int e = arena_commit(c, ps.arena, r.slot, 0, st)) return e;  // (direct route: drains the write-combining buffers)
       GapTabArgs ta;
       memset(&ta, 0, sizeof(ta));
-      ta.base = (const char*)P.dev;
-      ta.regions = (char*)ps.arena.dev[r.slot];
-      ta.stride = r.stride;
+      paired_tab_geometry(ta, ps, ps.arena.dev[r.slot], r.stride, r.bw, (unsigned char*)ps.arena.dev[r.slot] + r.stride * (size_t)chunk, r.chg_bytes);
       for (int mt = 0; mt < 2; mt++) {
-        ta.off_occ[mt] = P.off_occ[mt]; ta.bytes_occ[mt] = r.bw[mt] * sizeof(Occ12);
-        ta.off_lo[mt] = P.off_lo[mt]; ta.bytes_lo[mt] = ps.image[mt].multi_off.size() * sizeof(int32_t);
-        ta.off_m[mt] = P.off_m[mt]; ta.bytes_m[mt] = ps.image[mt].multi.size() * sizeof(OccQuad);
         ta.n_occ[mt] = (int)ps.image[mt].occ12.size();
         ta.n_lists[mt] = ps.image[mt].multi_off.empty() ? 0 : (int)ps.image[mt].multi_off.size() - 1;
         ta.n_multi[mt] = (int)ps.image[mt].multi.size();
         ta.first_rank[mt] = r.first_rank[mt];
-        ta.chg_bytes[mt] = r.chg_bytes[mt];
       }
-      ta.chg[0] = (unsigned char*)ps.arena.dev[r.slot] + r.stride * (size_t)chunk;
-      ta.chg[1] = ta.chg[0] + r.chg_bytes[0];
       ta.slot = r.path_slot;
       ta.n_sets = n;
       for (int k = 0; k < n; k++) ta.delta[k] = lens[done + k] - base_len;
@@ -205,21 +191,9 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
       const unsigned char* chg[2] = {ta.chg[0], ta.chg[1]};
       if (int e = launch_paired_multi(c, ps, 0, n, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.dev[r.slot], r.stride, st, chg)) return e;
     }
-    bool spun = false;
-    if (int e = wait_host_partials(c, &spun)) return e;
-    if (!spun) { if (int e2 = collect_events(c)) return e2; }
-    if (int e = paired_counts_after_wait(c)) return e;
+    if (int e = multi_wait(c)) return e;
+    multi_collect(c, n, part.data(), false);  // (no penalised set comes this way: gap_device_capable)
     for (int k = 0; k < n; k++) {
-      for (size_t i = 0; i < nps; i++) {
-        PairedSet& ps = *c->paireds[i];
-        double* out = part.data() + ((size_t)k * nps + i) * 4;
-        out[0] = out[1] = out[2] = 0;
-        if (ps.last_blocks[k] > 0)
-          finisher_order_sum((const double*)ps.h_part_sum.p + (size_t)k * ps.host_part_stride, (const int*)ps.h_part_zero.p + (size_t)k * ps.host_part_stride,
-                             ps.last_blocks[k], &out[0], &out[1]);
-        out[3] = (double)ps.mate[0].n_local();
-        ps.last_bad_bases = 0;
-      }
       const int32_t at = done + k;
       if (int e = combine(c, part.data() + (size_t)k * 4 * ns, &probs_out[at], zeros_out ? zeros_out + (size_t)at * 2 * ns : nullptr, tls[k])) return e;
       if (tls_out) tls_out[at] = tls[k];

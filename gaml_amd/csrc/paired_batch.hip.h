@@ -1,12 +1,18 @@
 // paired_batch.hip.h -- gaml_hip_calc_prob_batch over paired sets: per-set tables from patches / whole, one pass over the records
 // (one translation unit with gaml_hip.hip, which includes this file at the place its contents used to stand)
+//
+//   batch_fast_capable    may this context's batches take the one-pass routes at all
+//   MultiPass, multi_wait / _drain / _collect   the frame of a multi-set pass: blocking scope, two-launch pacing, the wait,
+//                         the hand-over with launches in flight, the results -- shared with gap_profile_device
+//   batch_chunk_patched   a chunk of up to kMaxSets sets, their tables built on the device from the resident copy + patches
+//   batch_chunk_fast      the same with whole tables per set, written by the host (takes over when patches do not do)
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------------
 // gaml_hip_calc_prob_batch, fast path: up to kMaxSets path sets in ONE pass over the records of every paired set
 // (paired_score_multi_kernel). The host plans the sets one after the other straight into consecutive regions of one
 // arena slot; then one launch per read set, one wait. Contexts with other kinds of read sets or without a memo take the
-// sequential path below (same results). A set with a coverage penalty goes along: its path sets mark into bitmaps of their
+// sequential path of gaml_hip_calc_prob_batch (same results). A set with a coverage penalty goes along: its path sets mark into bitmaps of their
 // own, one sweep dispatch per launch (launch_paired_multi); the wait is then a real stream wait, one per chunk.
 // ---------------------------------------------------------------------------------------------------------
 static bool batch_fast_capable(const gaml_hip_ctx* c) {
@@ -16,7 +22,60 @@ static bool batch_fast_capable(const gaml_hip_ctx* c) {
   return true;
 }
 
-// The same with the sets' tables built on the device (batch_tables_kernel): on a large-BAR device the resident copy
+// ---------------------------------------------------------------------------------------------------------
+// The frame of a multi-set pass, shared by the routes that feed paired_score_multi_kernel: batch_chunk_patched and
+// batch_chunk_fast below, gap_profile_device (gap_profile.hip.h). A route says how its regions are sized, what it writes
+// per set, which table kernel it launches and when it gives up; the rest is here.
+// ---------------------------------------------------------------------------------------------------------
+// The blocking scope (results in pinned host memory; on every way out the context is as a blocking call leaves it), and
+// the pacing of the two batch routes: a chunk of more than 4 sets goes out in two launches, the host plans the second
+// half while the device scores the first.
+struct MultiPass {
+  gaml_hip_ctx* c;
+  int n, half, launched = 0;  // (where the batch is cut makes no measurable difference: 13.1-14.8 us per set for 1+7 .. 6+2)
+  MultiPass(gaml_hip_ctx* ctx, int n_sets) : c(ctx), n(n_sets), half(n_sets > 4 ? (n_sets + 1) / 2 : n_sets) { c->host_results = true; }
+  ~MultiPass() { c->host_results = false; c->pending_open = false; }
+  MultiPass(const MultiPass&) = delete;
+  bool due(int k) const { return k + 1 == half || k + 1 == n; }  // set k is planned: sets [launched, k + 1) go out now
+};
+
+// every launch of the pass has landed (spinning on the partials where that is safe), the delta lists' counts are exact
+static int multi_wait(gaml_hip_ctx* c) {
+  bool spun = false;
+  if (int e = wait_host_partials(c, &spun)) return e;
+  if (!spun) { if (int e = collect_events(c)) return e; }
+  return paired_counts_after_wait(c);
+}
+// best effort, before a route hands its chunk on with launches in flight (the route that takes over reports what is wrong)
+static void multi_drain(gaml_hip_ctx* c) {
+  bool spun = false;
+  (void)wait_host_partials(c, &spun);
+  if (!spun) (void)collect_events(c);
+}
+
+// after multi_wait: out[(k * read sets + i) * 4 ..] = {sum, floored, bad bases, reads} of set k, added up in the finisher
+// kernel's order from the set's stripe of pinned partials. record_bad: the penalised sets' counters (handed over behind
+// the partials, store_bad_multi_kernel) and the batch's bookkeeping of them; a pass without penalised sets leaves both alone.
+static void multi_collect(gaml_hip_ctx* c, int n, double* partials_out, bool record_bad) {
+  const size_t nps = c->paireds.size();
+  for (int k = 0; k < n; k++)
+    for (size_t i = 0; i < nps; i++) {
+      PairedSet& ps = *c->paireds[i];
+      double* out = partials_out + ((size_t)k * nps + i) * 4;
+      out[0] = out[1] = out[2] = 0;
+      if (ps.last_blocks[k] > 0)
+        finisher_order_sum((const double*)ps.h_part_sum.p + (size_t)k * ps.host_part_stride, (const int*)ps.h_part_zero.p + (size_t)k * ps.host_part_stride,
+                           ps.last_blocks[k], &out[0], &out[1]);
+      out[3] = (double)ps.mate[0].n_local();
+      if (record_bad) {
+        if (ps.cfg.penalty_constant > 0 && ps.last_blocks[k] > 0) out[2] = (double)((const unsigned long long*)ps.h_bad.p)[k];
+        ps.batch_bad.push_back((int64_t)out[2]);
+      }
+      ps.last_bad_bases = (int64_t)out[2];
+    }
+}
+
+// A chunk with the sets' tables built on the device (batch_tables_kernel): on a large-BAR device the resident copy
 // of the tables mirrors the previous call's path set, and candidates differ from it -- and from each other -- in a
 // few dozen entries. Returns 1 when this chunk cannot go that way (tables rebuilt as a whole, list changes, growth
 // past the resident capacities): the caller takes the full-tables route, which plans the chunk again.
@@ -37,17 +96,13 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     std::vector<int32_t> touched[2];  // union of the changed entries: the resident copy follows after the batch
   };
   std::vector<PerSet> per(nps);
-  c->host_results = true;
-  struct Reset { gaml_hip_ctx* c; ~Reset() { c->host_results = false; c->pending_open = false; } } reset{c};
+  MultiPass pass(c, n);
   for (size_t i = 0; i < nps; i++) {
     PairedSet& ps = *c->paireds[i];
     if (int e = prepare_paired_tables(c, ps)) return e;
     PairedSet::Persist& P = ps.persist;
     // bring the copy up to the images (made here if no blocking call has yet; entries changed by a call that did not go through it)
-    if (!P.valid || ps.image[0].changed_all || ps.image[1].changed_all || !ps.image[0].changed.empty() || !ps.image[1].changed.empty() ||
-        ps.image[0].lists_changed || ps.image[1].lists_changed) {
-      if (int e = paired_persist_update(c, ps, 2.0, st)) return e;
-    }
+    if (paired_persist_stale(ps)) { if (int e = paired_persist_update(c, ps, 2.0, st)) return e; }
     PerSet& r = per[i];
     r.stride = align16(P.bytes);
     if (ps.cfg.penalty_constant > 0) {
@@ -64,10 +119,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
       r.cov_cap = (size_t)std::max(1, ps.planner.slot_count()) + all_paths + most + 16;
       r.stride = align16(r.cov_at + r.cov_cap * sizeof(int32_t));
     }
-    r.L.tfloor_off = P.off_tfloor;
-    r.L.l0 = OccLayout{P.off_occ[0], P.off_lo[0], P.off_m[0], P.off_lo[1] /* unused */};
-    r.L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.bytes};
-    r.L.sb_off = r.L.pb_off = r.L.so_off = r.L.st_off = 0; r.L.total = P.bytes;
+    r.L = paired_persist_layout(P);
     r.Ls.assign((size_t)n, r.L);
     r.prep.resize((size_t)n);
     r.patch_off.assign(2 * (size_t)n + 1, 0);
@@ -78,48 +130,36 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     const size_t bytes = r.stride * (size_t)n + r.tail_fixed + 2 * (r.chg_bytes[0] + r.chg_bytes[1]);
     if (int e = arena_acquire(c, ps.arena, bytes, st, &r.slot, &r.wp)) return e;
   }
-  auto give_up = [&](bool in_flight) -> int {  // the resident copies no longer mirror the images: rewritten as a whole next time
+  auto give_up = [&]() -> int {  // the resident copies no longer mirror the images: rewritten as a whole next time
     for (size_t i = 0; i < nps; i++) c->paireds[i]->persist.valid = false;
-    if (in_flight) { bool spun = false; (void)wait_host_partials(c, &spun); if (!spun) (void)collect_events(c); }
+    if (pass.launched > 0) multi_drain(c);
     return 1;
   };
-  const int half = n > 4 ? (n + 1) / 2 : n;  // (where the batch is cut makes no measurable difference: 13.1-14.8 us per set for 1+7 .. 6+2)
-  int launched = 0;
-  auto launch_upto = [&](int upto) -> int {
+  auto launch_sets = [&](int first, int upto) -> int {
     for (size_t i = 0; i < nps; i++) {
       PairedSet& ps = *c->paireds[i];
       PerSet& r = per[i];
-      const PairedSet::Persist& P = ps.persist;
       if (int e = paired_sync_tables(c, ps, st)) return e;
-      for (int k = launched; k < upto; k++) paired_pack_thresholds(ps, r.L, (double)(2 * (tls[k] == 0 ? 1 : tls[k])), r.wp + (size_t)k * r.stride);
+      for (int k = first; k < upto; k++) paired_pack_thresholds(ps, r.L.tfloor_off, (double)(2 * (tls[k] == 0 ? 1 : tls[k])), r.wp + (size_t)k * r.stride);
       char* tail = r.wp + r.stride * (size_t)n;
       int* d_off = (int*)(tail + align16(kPatchCap * sizeof(BatchPatch)));
       memcpy(d_off, r.patch_off.data(), (2 * (size_t)upto + 1) * sizeof(int));
       if (int e = arena_commit(c, ps.arena, r.slot, 0, st)) return e;  // (direct route: drains the write-combining buffers)
       BatchTabArgs ta;
-      ta.base = (const char*)P.dev;
-      ta.regions = (char*)ps.arena.dev[r.slot];
-      ta.stride = r.stride;
-      for (int mt = 0; mt < 2; mt++) {
-        ta.off_occ[mt] = P.off_occ[mt]; ta.bytes_occ[mt] = r.bw[mt] * sizeof(Occ12);
-        ta.off_lo[mt] = P.off_lo[mt]; ta.bytes_lo[mt] = ps.image[mt].multi_off.size() * sizeof(int32_t);
-        ta.off_m[mt] = P.off_m[mt]; ta.bytes_m[mt] = ps.image[mt].multi.size() * sizeof(OccQuad);
-      }
-      ta.patches = (const BatchPatch*)((const char*)ps.arena.dev[r.slot] + r.stride * (size_t)n);
-      ta.patch_off = (const int*)((const char*)ta.patches + align16(kPatchCap * sizeof(BatchPatch)));
-      ta.first = launched;
-      ta.n_sets = upto - launched;
-      char* chg0 = (char*)ps.arena.dev[r.slot] + r.stride * (size_t)n + r.tail_fixed + (size_t)(r.launches & 1) * (r.chg_bytes[0] + r.chg_bytes[1]);
-      ta.chg[0] = (unsigned char*)chg0; ta.chg[1] = (unsigned char*)chg0 + r.chg_bytes[0];
-      ta.chg_bytes[0] = r.chg_bytes[0]; ta.chg_bytes[1] = r.chg_bytes[1];
+      char* dev_tail = (char*)ps.arena.dev[r.slot] + r.stride * (size_t)n;
+      paired_tab_geometry(ta, ps, ps.arena.dev[r.slot], r.stride, r.bw,
+                          (unsigned char*)dev_tail + r.tail_fixed + (size_t)(r.launches & 1) * (r.chg_bytes[0] + r.chg_bytes[1]), r.chg_bytes);  // (the other launch's may still be read)
+      ta.patches = (const BatchPatch*)dev_tail;
+      ta.patch_off = (const int*)(dev_tail + align16(kPatchCap * sizeof(BatchPatch)));
+      ta.first = first;
+      ta.n_sets = upto - first;
       r.launches++;
-      hipLaunchKernelGGL(batch_tables_kernel, dim3((unsigned)(upto - launched) + 1, 2), dim3(1024), 0, st, ta);
+      hipLaunchKernelGGL(batch_tables_kernel, dim3((unsigned)(upto - first) + 1, 2), dim3(1024), 0, st, ta);
       HIP_TRY(c, hipGetLastError());
       const unsigned char* chg[2] = {ta.chg[0], ta.chg[1]};
-      if (int e = launch_paired_multi(c, ps, launched, upto - launched, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.dev[r.slot], r.stride, st,
+      if (int e = launch_paired_multi(c, ps, first, upto - first, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.dev[r.slot], r.stride, st,
                                       KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_NO_CAPTURE ? nullptr : chg)) return e;  // every set resolves every pair (A/B)
     }
-    launched = upto;
     return 0;
   };
   for (int k = 0; k < n; k++) {
@@ -142,7 +182,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
           fprintf(stderr, "batch set %d: not a patch (all %d %d, lists %d %d, windows %zu/%zu %zu/%zu, patches %zu + %zu + %zu)\n", k, (int)im[0].changed_all, (int)im[1].changed_all,
                   (int)im[0].lists_changed, (int)im[1].lists_changed, im[0].occ12.size(), P.cap_w[0], im[1].occ12.size(), P.cap_w[1], r.n_patches, im[0].changed.size(), im[1].changed.size());
         c->pending_open = false;
-        return give_up(launched > 0);
+        return give_up();
       }
       if (ps.cfg.penalty_constant > 0) {  // this set's coverage layout into its region (fenced with the thresholds, arena_commit)
         paired_cov_layout(r.prep[(size_t)k], r.cov_at, r.Ls[(size_t)k]);
@@ -161,18 +201,14 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
       }
     }
     c->pending_open = false;
-    if (k + 1 == half && half < n) { if (int e = launch_upto(half)) return e; }
+    if (pass.due(k)) { if (int e = launch_sets(pass.launched, k + 1)) return e; pass.launched = k + 1; }
   }
-  if (int e = launch_upto(n)) return e;
   if (getenv("GAML_HIP_TRACE_HOST")) {
     fprintf(stderr, "batch of %d sets, patch entries per set (mate 1 + mate 2):", n);
     for (int k = 0; k < n; k++) fprintf(stderr, " %d+%d", per[0].patch_off[2 * k + 1] - per[0].patch_off[2 * k], per[0].patch_off[2 * k + 2] - per[0].patch_off[2 * k + 1]);
     fprintf(stderr, "\n");
   }
-  bool spun = false;
-  if (int e = wait_host_partials(c, &spun)) return e;
-  if (!spun) { if (int e2 = collect_events(c)) return e2; }
-  if (int e = paired_counts_after_wait(c)) return e;
+  if (int e = multi_wait(c)) return e;
   // the device is done with the resident copies: they follow the images (now the last set's)
   for (size_t i = 0; i < nps; i++) {
     PairedSet& ps = *c->paireds[i];
@@ -182,32 +218,19 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
   }
   _mm_sfence();
   for (size_t i = 0; i < nps; i++) c->paireds[i]->batches_patched++;
-  for (int k = 0; k < n; k++)
-    for (size_t i = 0; i < nps; i++) {
-      PairedSet& ps = *c->paireds[i];
-      double* out = partials_out + ((size_t)k * nps + i) * 4;
-      out[0] = out[1] = out[2] = 0;
-      if (ps.last_blocks[k] > 0)
-        finisher_order_sum((const double*)ps.h_part_sum.p + (size_t)k * ps.host_part_stride, (const int*)ps.h_part_zero.p + (size_t)k * ps.host_part_stride,
-                           ps.last_blocks[k], &out[0], &out[1]);
-      out[3] = (double)ps.mate[0].n_local();
-      // a penalised set: the launch's counters, handed over behind the partials (store_bad_multi_kernel)
-      if (ps.cfg.penalty_constant > 0 && ps.last_blocks[k] > 0) out[2] = (double)((const unsigned long long*)ps.h_bad.p)[k];
-      ps.batch_bad.push_back((int64_t)out[2]);
-      ps.last_bad_bases = (int64_t)out[2];
-    }
+  multi_collect(c, n, partials_out, true);
   return 0;
 }
 
-// returns 1 when a set's tables did not fit the region reserved for it (the caller falls back for this chunk)
+// A chunk with whole tables per set, packed by the host into the regions. Returns 1 when a set's tables did not fit the
+// region reserved for it (the caller's sequential path takes this chunk; the region is larger next time)
 static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const int64_t* offs, const int32_t* set_offs,
                             double* partials_out, int32_t* tls) {
   hipStream_t st = c->stream;
   const size_t nps = c->paireds.size();
   struct PerSet { int slot = 0; char* wp = nullptr; size_t stride = 0, cap_w[2] = {0, 0}; std::vector<PairedLayout> L; std::vector<PairedPrep> prep; };
   std::vector<PerSet> per(nps);
-  c->host_results = true;
-  struct Reset { gaml_hip_ctx* c; ~Reset() { c->host_results = false; c->pending_open = false; } } reset{c};
+  MultiPass pass(c, n);
   for (size_t i = 0; i < nps; i++) {
     PairedSet& ps = *c->paireds[i];
     if (int e = prepare_paired_tables(c, ps)) return e;
@@ -223,19 +246,15 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
     per[i].L.resize((size_t)n);
     per[i].prep.resize((size_t)n);
   }
-  // the batch goes out in two launches: the host plans the second half while the device scores the first
-  const int half = n > 4 ? (n + 1) / 2 : n;  // (where the batch is cut makes no measurable difference: 13.1-14.8 us per set for 1+7 .. 6+2)
-  int launched = 0;
-  auto launch_upto = [&](int upto) -> int {
+  auto launch_sets = [&](int first, int upto) -> int {
     for (size_t i = 0; i < nps; i++) {
       PairedSet& ps = *c->paireds[i];
       if (int e = paired_sync_tables(c, ps, st)) return e;
-      for (int k = launched; k < upto; k++) paired_pack_thresholds(ps, per[i].L[(size_t)k], (double)(2 * (tls[k] == 0 ? 1 : tls[k])), per[i].wp + (size_t)k * per[i].stride);
+      for (int k = first; k < upto; k++) paired_pack_thresholds(ps, per[i].L[(size_t)k].tfloor_off, (double)(2 * (tls[k] == 0 ? 1 : tls[k])), per[i].wp + (size_t)k * per[i].stride);
       // (the staged route copies the regions written so far; the direct route only drains the write-combining buffers)
       if (int e = arena_commit(c, ps.arena, per[i].slot, per[i].stride * (size_t)upto, st)) return e;
-      if (int e = launch_paired_multi(c, ps, launched, upto - launched, per[i].L.data(), per[i].prep.data(), tls, (const char*)ps.arena.dev[per[i].slot], per[i].stride, st)) return e;
+      if (int e = launch_paired_multi(c, ps, first, upto - first, per[i].L.data(), per[i].prep.data(), tls, (const char*)ps.arena.dev[per[i].slot], per[i].stride, st)) return e;
     }
-    launched = upto;
     return 0;
   };
   for (int k = 0; k < n; k++) {
@@ -250,34 +269,17 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
       if (fits) { per[i].L[(size_t)k] = paired_layout(ps, p, per[i].cap_w); fits = per[i].L[(size_t)k].total <= per[i].stride; }
       if (!fits) {  // the tables outgrew the region reserved per set: the sequential path takes this chunk (after what is in flight)
         ps.batch_slack += 24 * 16384 + 2 * per[i].stride;
-        if (launched > 0) { bool spun = false; (void)wait_host_partials(c, &spun); if (!spun) (void)collect_events(c); }
+        if (pass.launched > 0) multi_drain(c);
         return 1;
       }
       paired_pack(ps, p, per[i].L[(size_t)k], per[i].wp + (size_t)k * per[i].stride);
     }
     c->pending_open = false;
-    if (k + 1 == half && half < n) { if (int e = launch_upto(half)) return e; }
+    if (pass.due(k)) { if (int e = launch_sets(pass.launched, k + 1)) return e; pass.launched = k + 1; }
   }
-  if (int e = launch_upto(n)) return e;
-  bool spun = false;
-  if (int e = wait_host_partials(c, &spun)) return e;
-  if (!spun) { if (int e2 = collect_events(c)) return e2; }
-  if (int e = paired_counts_after_wait(c)) return e;
+  if (int e = multi_wait(c)) return e;
   for (size_t i = 0; i < nps; i++) c->paireds[i]->batches_full++;
-  for (int k = 0; k < n; k++)
-    for (size_t i = 0; i < nps; i++) {
-      PairedSet& ps = *c->paireds[i];
-      double* out = partials_out + ((size_t)k * nps + i) * 4;
-      out[0] = out[1] = out[2] = 0;
-      if (ps.last_blocks[k] > 0)
-        finisher_order_sum((const double*)ps.h_part_sum.p + (size_t)k * ps.host_part_stride, (const int*)ps.h_part_zero.p + (size_t)k * ps.host_part_stride,
-                           ps.last_blocks[k], &out[0], &out[1]);
-      out[3] = (double)ps.mate[0].n_local();
-      // a penalised set: the launch's counters, handed over behind the partials (store_bad_multi_kernel)
-      if (ps.cfg.penalty_constant > 0 && ps.last_blocks[k] > 0) out[2] = (double)((const unsigned long long*)ps.h_bad.p)[k];
-      ps.batch_bad.push_back((int64_t)out[2]);
-      ps.last_bad_bases = (int64_t)out[2];
-    }
+  multi_collect(c, n, partials_out, true);
   return 0;
 }
 

@@ -6,7 +6,11 @@
 //   paired_layout / _pack      per path set: where its tables sit in an arena slot, and the bytes
 //   arena_acquire / _commit    the slot itself: device memory the HOST writes directly (PCIe BAR), or pinned staging
 //                              + copy when the device has no large BAR
+//   paired_persist_update      the resident copy of the tables (blocking calls on a large-BAR device), patched in place;
+//                              paired_persist_stale: does it lag behind the images; paired_persist_layout: a region laid out
+//                              like it; paired_tab_geometry: what the kernels that copy it into such regions are told
 //   paired_base_args / paired_set_view   kernel arguments: what is common to all path sets / what one set changes
+//                              (paired_persist_view: the same of the resident copy)
 //   launch_paired              one path set: ONE dispatch (paired_score_kernel) on the warm path
 //   launch_paired_multi        up to 8 path sets in one pass over the records (paired_score_multi_kernel)
 #pragma once
@@ -186,14 +190,15 @@ PairedLayout paired_layout(const PairedSet& s, const PairedPrep& p, const size_t
 }
 
 // the thresholds on t per length code for this set's 2T -- AFTER paired_sync_tables (a rebuild renumbers the codes)
-void paired_pack_thresholds(const PairedSet& s, const PairedLayout& L, double two_T, char* dst) {
+// (tfloor_off: PairedLayout::tfloor_off of the region, Persist::off_tfloor of the resident copy)
+void paired_pack_thresholds(const PairedSet& s, size_t tfloor_off, double two_T, char* dst) {
   double tf[256];
   const size_t nc = std::min<size_t>(256, s.pt.len_combo.size());
   for (size_t ci = 0; ci < nc; ci++) {
     const int L0 = (int)(s.pt.len_combo[ci] & 0xffff), L1 = (int)(s.pt.len_combo[ci] >> 16);
     tf[ci] = tfloor_for(s.floor_tab[L0 + L1], two_T);
   }
-  if (nc) memcpy(dst + L.tfloor_off, tf, nc * sizeof(double));
+  if (nc) memcpy(dst + tfloor_off, tf, nc * sizeof(double));
 }
 
 // write-only (dst may be device memory behind the PCIe BAR: never read it back)
@@ -251,6 +256,42 @@ int arena_release(gaml_hip_ctx* c, Arena& A, int k, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------
 // the resident copy of the tables (blocking calls on a large-BAR device): patched in place through the BAR
 // ---------------------------------------------------------------------------------------------------------
+// must the copy be written as a whole / does it lag behind the images at all (never made, given up by a batch, or entries
+// and lists changed by a call that did not go through it): what a route that reads the copy asks before paired_persist_update
+bool paired_persist_whole(const PairedSet& s) { return !s.persist.valid || s.image[0].changed_all || s.image[1].changed_all; }
+bool paired_persist_stale(const PairedSet& s) {
+  const OccImage* im = s.image;
+  return paired_persist_whole(s) || !im[0].changed.empty() || !im[1].changed.empty() || im[0].lists_changed || im[1].lists_changed;
+}
+
+// a region "laid out like the resident copy" (what batch_tables_kernel / gap_tables_kernel fill): no coverage layout
+PairedLayout paired_persist_layout(const PairedSet::Persist& P) {
+  PairedLayout L;
+  L.tfloor_off = P.off_tfloor;
+  L.l0 = OccLayout{P.off_occ[0], P.off_lo[0], P.off_m[0], P.off_lo[1] /* unused */};
+  L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.bytes};
+  L.sb_off = L.pb_off = L.so_off = L.st_off = 0; L.total = P.bytes;
+  return L;
+}
+
+// The copy geometry that BatchTabArgs and GapTabArgs share (field for field the same names): from the resident copy into
+// regions of `stride` bytes laid out like it, entries[mt] table entries per mate and the lists there are; behind it the
+// launch's MultiSets::chg bytes, mate 2's behind mate 1's.
+template <class TabArgs>
+void paired_tab_geometry(TabArgs& ta, const PairedSet& s, void* regions, size_t stride, const size_t* entries, unsigned char* chg, const size_t* chg_bytes) {
+  const PairedSet::Persist& P = s.persist;
+  ta.base = (const char*)P.dev;
+  ta.regions = (char*)regions;
+  ta.stride = stride;
+  for (int mt = 0; mt < 2; mt++) {
+    ta.off_occ[mt] = P.off_occ[mt]; ta.bytes_occ[mt] = entries[mt] * sizeof(Occ12);
+    ta.off_lo[mt] = P.off_lo[mt]; ta.bytes_lo[mt] = s.image[mt].multi_off.size() * sizeof(int32_t);
+    ta.off_m[mt] = P.off_m[mt]; ta.bytes_m[mt] = s.image[mt].multi.size() * sizeof(OccQuad);
+    ta.chg_bytes[mt] = chg_bytes[mt];
+  }
+  ta.chg[0] = chg; ta.chg[1] = chg + chg_bytes[0];
+}
+
 // cov_L (penalty_constant > 0): receives where this call's coverage layout sits in the copy (offsets from Persist::dev)
 int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream_t st, const PairedPrep* p = nullptr, PairedLayout* cov_L = nullptr) {
   PairedSet::Persist& P = s.persist;
@@ -265,7 +306,7 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
     need_m[mt] = std::max<size_t>(1, im[mt].multi.size());
     if (need_w[mt] > P.cap_w[mt] || need_lo[mt] > P.cap_lo[mt] || need_m[mt] > P.cap_m[mt]) relayout = true;
   }
-  bool full = !P.valid || im[0].changed_all || im[1].changed_all;
+  bool full = paired_persist_whole(s);
   if (relayout) {
     size_t at = align16(256 * sizeof(double));  // thresholds per length code
     P.off_tfloor = 0;
@@ -309,9 +350,7 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
     }
     t.take_changed();
   }
-  PairedLayout L;  // only the threshold offset is used here
-  L.tfloor_off = P.off_tfloor;
-  paired_pack_thresholds(s, L, two_T, wp);
+  paired_pack_thresholds(s, P.off_tfloor, two_T, wp);
   if (cov_L) {  // fenced with the thresholds below; never read back
     paired_cov_layout(*p, P.off_cov, *cov_L);
     paired_cov_pack(*p, *cov_L, wp);
@@ -326,23 +365,6 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
 double paired_tfloor0(const PairedSet& s, double two_T) {
   if (s.pt.len_combo.empty()) return 0.0;
   return tfloor_for(s.floor_tab[(s.pt.len_combo[0] & 0xffff) + (s.pt.len_combo[0] >> 16)], two_T);
-}
-
-void paired_persist_view(const PairedSet& s, int32_t total_len, SetDev& sd) {
-  const PairedSet::Persist& P = s.persist;
-  const char* base = (const char*)P.dev;
-  for (int mt = 0; mt < 2; mt++) {
-    sd.occ12[mt] = (const Occ12*)(base + P.off_occ[mt]);
-    sd.multi_off[mt] = (const int*)(base + P.off_lo[mt]);
-    sd.multi[mt] = (const int4*)(base + P.off_m[mt]);
-  }
-  sd.tfloor_c = (const double*)(base + P.off_tfloor);
-  const int tl = total_len == 0 ? 1 : total_len;
-  sd.two_T = (double)(2 * tl);
-  sd.tfloor0 = paired_tfloor0(s, sd.two_T);
-  sd.log_two_T = std::log(sd.two_T);
-  sd.part_sum = nullptr; sd.part_zero = nullptr;
-  sd.cov_bits = nullptr; sd.slot_base = nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -449,6 +471,10 @@ void paired_set_view(const PairedSet& s, const PairedLayout& L, const char* aren
   sd.part_sum = nullptr; sd.part_zero = nullptr;
   sd.cov_bits = nullptr; sd.slot_base = nullptr;
 }
+// ... and the same of the resident copy
+void paired_persist_view(const PairedSet& s, int32_t total_len, SetDev& sd) {
+  paired_set_view(s, paired_persist_layout(s.persist), (const char*)s.persist.dev, total_len, sd);
+}
 
 void paired_apply_set(PairedArgs& a, const SetDev& sd) {
   for (int mt = 0; mt < 2; mt++) { a.m[mt].occ12 = sd.occ12[mt]; a.m[mt].occ = nullptr; a.occ12[mt] = sd.occ12[mt]; a.m[mt].multi_off = sd.multi_off[mt]; a.m[mt].multi = sd.multi[mt]; }
@@ -518,9 +544,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   s.occdev.check_dup = s.occdev.taken;
   if (s.occdev.taken) {
     // device route: occ_scatter_kernel (queued in pass 2) builds this call's tables; only the thresholds go through the BAR
-    PairedLayout Lt;
-    Lt.tfloor_off = s.persist.off_tfloor;
-    paired_pack_thresholds(s, Lt, (double)(2 * tl), (char*)s.persist.dev);
+    paired_pack_thresholds(s, s.persist.off_tfloor, (double)(2 * tl), (char*)s.persist.dev);
     _mm_sfence();
     paired_persist_view(s, total_len, sd);
     for (int mt = 0; mt < 2; mt++) sd.occ12[mt] = occdev_table(s, mt);
@@ -535,7 +559,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     char* wp = nullptr;
     if (int e = arena_acquire(c, s.arena, L.total, st, &slot, &wp)) return e;
     paired_pack(s, p, L, wp);
-    paired_pack_thresholds(s, L, (double)(2 * tl), wp);
+    paired_pack_thresholds(s, L.tfloor_off, (double)(2 * tl), wp);
     if (int e = arena_commit(c, s.arena, slot, L.total, st)) return e;
     arena = (const char*)s.arena.dev[slot];
     paired_set_view(s, L, arena, total_len, sd);
@@ -733,16 +757,9 @@ int launch_paired_multi(gaml_hip_ctx* c, PairedSet& s, int first, int n_sets, co
     unsigned long long* counters = (unsigned long long*)cov_base;
     for (int k = 0; k < n_sets; k++) {
       const int g = first + k;
-      const char* region = arena + (size_t)g * stride;
       CovArgs& v = ca.set[k];
+      v = paired_cov_args(s, preps[g], L[g], arena + (size_t)g * stride);  // but the set's own bitmap and counter
       v.bits = ms.set[k].cov_bits;
-      v.path_base = (const int*)(region + L[g].pb_off);
-      v.start_off = (const int*)(region + L[g].so_off);
-      v.starts = (const int*)(region + L[g].st_off);
-      v.n_paths = preps[g].n_paths;
-      v.total_words = preps[g].total_bits / 32;
-      v.cov_move = s.cfg.step;
-      v.far = s.cfg.insert_mean + 5 * s.cfg.insert_std;
       v.bad = counters + k;
       ca.block_off[k + 1] = ca.block_off[k] + (v.total_words > 0 ? grid_for(v.total_words) : 0);  // (the empty assembly: no blocks, its counter stays 0)
     }

@@ -198,6 +198,95 @@ def test_candidate_batches_build_their_tables_on_the_device(two_sets):
     assert ctxs[0][1].calc_prob(last)[0] == ctxs[4][1].calc_prob(last)[0]
 
 
+def _hand_over_case():
+    """A base assembly of a dozen paths, and candidates one edit of one path away from it (few enough paths change from
+    candidate to candidate for the planner to follow them path by path: the images change in a few entries)."""
+    g, reads, _, make = _paired_only()
+    walk = synth.genome_walk(g)
+    base = [walk[i:i + 8] for i in range(0, len(walk) - 7, 8)]
+    assert len(base) >= 10, len(base)
+
+    def edit(k, how):
+        i, p = k + 1, base[k + 1]
+        new = {"cut": [p[:3], p[3:]], "drop": [p[:4] + p[5:]], "dup": [p[:5] + p[2:5] + p[5:]]}[how]
+        return base[:i] + new + base[i + 1:]
+    return g, base, edit, make
+
+
+def _warm_pair(make, base, cands):
+    """Two contexts in the same device state, every window of `cands` aligned and folded into the record tables."""
+    ctxs = [make(), make()]
+    for c in ctxs:
+        c.calc_prob(base)
+        for s in cands:
+            c.calc_prob(s)
+        c.compact_tables()
+        c.calc_prob(base)
+    return ctxs
+
+
+def test_patched_batch_hands_its_chunk_over_after_the_first_launch():
+    """A chunk of 8 candidates whose sixth changes the occurrence lists: the route that builds the tables from patches has
+    launched sets 0-3 by then, waits for them, invalidates the resident copy and hands the chunk to the full-tables
+    route. Values, floored counts and total lengths are those of single calls bit for bit, the chunk counts as a
+    full-tables one, and the blocking call that follows finds a resident copy rewritten as a whole."""
+    g, base, edit, make = _hand_over_case()
+    cands = [edit(k, how) for k, how in enumerate(["cut", "drop", "cut", "drop", "cut", "dup", "cut", "drop"])]
+    one, many = _warm_pair(make, base, cands)
+    before = many.table_stats(0)
+    got = many.calc_prob_batch(cands)
+    after = many.table_stats(0)
+    again = many.calc_prob(cands[-1])  # the images hold this very set: nothing but the invalidation makes the copy follow
+    assert after["batches_full"] - before["batches_full"] == 1 and after["batches_patched"] == before["batches_patched"], (before, after)
+    want = [one.calc_prob(s) for s in cands]
+    assert again[0] == want[-1][0] and again[1].tolist() == want[-1][1].tolist()
+    same = [many.calc_prob(s) for s in cands]
+    for b, w, s in zip(got, want, same):
+        assert b[0] == w[0] == s[0], (b[0], w[0], s[0])
+        assert b[1].tolist() == w[1].tolist() == s[1].tolist() and b[2] == w[2] == s[2]
+    # the same chunk without the sixth candidate's repeat goes through on patches
+    plain = cands[:5] + [cands[6], cands[7], cands[0]]
+    many.calc_prob(base)
+    before = many.table_stats(0)
+    got = many.calc_prob_batch(plain)
+    after = many.table_stats(0)
+    assert after["batches_patched"] - before["batches_patched"] == 1 and after["batches_full"] == before["batches_full"], (before, after)
+    assert [b[0] for b in got] == [one.calc_prob(s)[0] for s in plain]
+
+
+def test_full_tables_batch_outgrown_after_its_first_launch():
+    """The full-tables route reserves room for 256 windows the chunk itself may add. Sets 0-3 (launched) add a handful, each
+    of sets 4-7 -- the nodes in a random order -- some hundred per mate to a cold context: the route waits for what is in
+    flight and the sequential path takes the chunk. Neither batch counter moves; the values are those of single calls
+    (cold: the delta lists fill in another order, last bits of the sum -- the bound of the cold cases above)."""
+    from gaml_amd import api
+    g, base, edit, make = _hand_over_case()
+    walk = synth.genome_walk(g)
+    rng = np.random.default_rng(17)
+    cands = [edit(k, "cut") for k in range(4)]
+    for _ in range(4):
+        cands.append([[walk[i] ^ int(f) for i, f in zip(rng.permutation(len(walk)), rng.integers(0, 2, len(walk)))]])
+    one, many = make(), make()
+    many.debug_set_knob(api.Knob.BATCH_ROUTE, api.BatchRoute.FULL_TABLES)
+    one.calc_prob(base); many.calc_prob(base)
+    aligned = one.aligner_stats()["windows"]
+    want = [one.calc_prob(s) for s in cands]
+    assert one.aligner_stats()["windows"] - aligned > 2 * (256 + 64), "the late sets must bring more windows per mate than the route reserves"
+    before = many.table_stats(0)
+    got = many.calc_prob_batch(cands)
+    after = many.table_stats(0)
+    assert (after["batches_patched"], after["batches_full"]) == (before["batches_patched"], before["batches_full"]), (before, after)
+    for b, w in zip(got, want):
+        assert b[2] == w[2] and b[1].tolist() == w[1].tolist()
+        assert abs(b[0] - w[0]) <= 1e-13 * abs(w[0]), (b[0], w[0])
+    # the region has grown with the chunk that outgrew it: the same sets now go through in one pass, bit for bit on one context
+    many.compact_tables()
+    many.calc_prob(base)
+    got = many.calc_prob_batch(cands)
+    assert many.table_stats(0)["batches_full"] - after["batches_full"] == 1
+    assert [b[0] for b in got] == [many.calc_prob(s)[0] for s in cands]
+
+
 def test_one_pass_batch_against_the_oracle():
     import oracle_py as op
     g, (m1, m2), sets, make = _paired_only(True, n=5000, seed=21)
