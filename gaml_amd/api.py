@@ -296,6 +296,9 @@ def _load():
         L.gaml_hip_debug_occ_route.argtypes = [vp, C.c_int, _i64p]
     if hasattr(L, "gaml_hip_debug_occ_check"):  # development build only
         L.gaml_hip_debug_occ_check.argtypes = [vp, C.c_int, _i64p]
+    if hasattr(L, "gaml_hip_debug_gap_cov_layout"):  # development build only
+        L.gaml_hip_debug_gap_cov_layout.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, vp]
+        L.gaml_hip_debug_gap_cov_layout.restype = C.c_int32
     if hasattr(L, "gaml_hip_debug_batch_bad_bases"):  # development build only
         L.gaml_hip_debug_batch_bad_bases.argtypes = [vp, C.c_int, C.c_void_p, C.c_int32]
         L.gaml_hip_debug_batch_bad_bases.restype = C.c_int32
@@ -322,6 +325,9 @@ def _load():
         L.gaml_hip_fix_gap_length.argtypes = [vp, _i32p, _i64p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
                                               C.c_int32, C.POINTER(C.c_int32)]
         L.gaml_hip_gap_stats.argtypes = [vp, _i64p]
+    if hasattr(L, "gaml_hip_set_gap_penalty_device"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_set_gap_penalty_device.argtypes = [vp, C.c_int32]
+        L.gaml_hip_get_gap_penalty_device.argtypes = [vp]
     if hasattr(L, "gaml_hip_debug_timeline"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_debug_timeline.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64]
     L.gaml_hip_last_phases.argtypes = [vp, _f64p]
@@ -665,6 +671,16 @@ class Context:
         self._check(_lib.gaml_hip_gap_stats(self._h, out))
         return dict(zip(("calls", "device_lengths", "fallback_lengths", "device_passes"), (int(x) for x in out)))
 
+    def set_gap_penalty_device(self, on):
+        """Let paired sets with a coverage penalty take the gap profile's device route (gaml_hip_set_gap_penalty_device);
+        off by default, or what GAML_HIP_GAP_PENALTY=device said when the context was made."""
+        if not hasattr(_lib, "gaml_hip_set_gap_penalty_device"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_set_gap_penalty_device")
+        self._check(_lib.gaml_hip_set_gap_penalty_device(self._h, 1 if on else 0))
+
+    def gap_penalty_device(self) -> bool:
+        return hasattr(_lib, "gaml_hip_get_gap_penalty_device") and _lib.gaml_hip_get_gap_penalty_device(self._h) == 1
+
     def calc_partials(self, paths):
         flat, offs = _flat(paths)
         tl = C.c_int32()
@@ -856,6 +872,19 @@ class Context:
         sb, pb, so = np.zeros(max(1, cnt[0]), np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
         sl, st = np.zeros(max(1, n), np.int32), np.zeros(max(1, cnt[2]), np.int32)
         _lib.gaml_hip_debug_cov_layout(self._h, rs, sb.ctypes.data, len(sb), pb.ctypes.data, so.ctypes.data, sl.ctypes.data, max(1, n), st.ctypes.data, len(st), cnt.ctypes.data)
+        return {"slot_base": sb[:cnt[0]], "path_base": pb, "start_off": so, "starts": st[:cnt[2]], "slots": sl[:n], "total_bits": int(cnt[3])}
+
+    def debug_gap_cov_layout(self, rs, g):
+        """debug_cov_layout's dict for region g of the last device pass of a gap profile: the layout gap_tables_kernel
+        derived for that pass's g-th length (gaml_hip_debug_gap_cov_layout)."""
+        cnt = np.zeros(4, np.int32)
+        z = np.zeros(2, np.int32)
+        n = _lib.gaml_hip_debug_gap_cov_layout(self._h, rs, g, z.ctypes.data, 0, z.ctypes.data, z.ctypes.data, z.ctypes.data, 0, z.ctypes.data, 0, cnt.ctypes.data)
+        if n < 0:
+            raise GamlHipError(n, "no coverage layout of a device gap pass: no penalty, no such pass or region")
+        sb, pb, so = np.zeros(max(1, cnt[0]), np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+        sl, st = np.zeros(max(1, n), np.int32), np.zeros(max(1, cnt[2]), np.int32)
+        _lib.gaml_hip_debug_gap_cov_layout(self._h, rs, g, sb.ctypes.data, len(sb), pb.ctypes.data, so.ctypes.data, sl.ctypes.data, max(1, n), st.ctypes.data, len(st), cnt.ctypes.data)
         return {"slot_base": sb[:cnt[0]], "path_base": pb, "start_off": so, "starts": st[:cnt[2]], "slots": sl[:n], "total_bits": int(cnt[3])}
 
     def debug_window_walk(self, rs, mate, wid) -> list:

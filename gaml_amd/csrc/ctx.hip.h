@@ -340,7 +340,9 @@ struct PairedSet {
   DevBuf cov_multi;
   size_t cov_multi_used = 0;
   PinBuf h_bad;
-  std::vector<int64_t> batch_bad;     // bad_bases per path set of the last gaml_hip_calc_prob_batch (gaml_hip_debug_batch_bad_bases)
+  std::vector<int64_t> batch_bad;     // bad_bases per path set of the last gaml_hip_calc_prob_batch, or per length of the last gap profile on the device route (gaml_hip_debug_batch_bad_bases)
+  // where the last device gap pass of a penalised set left its regions' coverage layouts (gaml_hip_debug_gap_cov_layout)
+  struct GapCov { int slot = -1, n = 0; size_t stride = 0, sb_off = 0, pb_off = 0, so_off = 0, st_off = 0; int n_sb = 0, n_pb = 0, n_st = 0; int32_t total_bits[8] = {0}; } gap_cov;
   Arena arena;                        // per-call tables (occurrence images, thresholds, coverage layout): ring, whole tables per call
   // Blocking calls on a large-BAR device keep ONE resident copy of the tables and patch it in place (the kernel
   // of the previous call is done when the call returns): a call that shares most paths with the previous one writes
@@ -473,6 +475,9 @@ struct PairedPrep {
 
 struct SetRef { int kind, idx; };
 
+// GAML_HIP_GAP_PENALTY=device: what a new context's gap_penalty_device starts as (read when the context is made)
+inline bool gap_penalty_env() { const char* e = getenv("GAML_HIP_GAP_PENALTY"); return e && strcmp(e, "device") == 0; }
+
 }  // namespace detail
 }  // namespace gaml
 
@@ -529,6 +534,7 @@ struct gaml_hip_ctx {
   // gaml_hip_gap_profile / gaml_hip_fix_gap_length (gap_profile.hip.h): {profile calls, lengths scored on the device route, on the
   // fallback, device passes}, and the path set with the base length in its gap (kept from call to call)
   int64_t gap_stats[4] = {0, 0, 0, 0};
+  bool gap_penalty_device = gap_penalty_env();  // penalised paired sets may take the gap profile's device route (gaml_hip_set_gap_penalty_device)
   std::vector<int32_t> gap_flat;
   std::vector<int64_t> gap_offs;
   // evaluation in progress (between eval_begin and eval_finish)

@@ -84,6 +84,30 @@ int32_t gaml_hip_debug_cov_layout(gaml_hip_ctx* c, int rs, int32_t* slot_base, i
   return n;
 }
 
+int32_t gaml_hip_debug_gap_cov_layout(gaml_hip_ctx* c, int rs, int g, int32_t* slot_base, int32_t cap_slots, int32_t* path_base, int32_t* start_off,
+                                       int32_t* slots, int32_t cap_paths, int32_t* starts, int32_t cap_starts, int32_t* counts4) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1 || c->device < 0) return -1;
+  PairedSet& ps = *c->paireds[c->handles[rs].idx];
+  const PairedSet::GapCov& G = ps.gap_cov;
+  if (G.slot < 0 || g < 0 || g >= G.n || !ps.arena.dev[G.slot]) return -1;  // no device gap pass of a penalised set yet, or no such region
+  if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+  const char* region = (const char*)ps.arena.dev[G.slot] + (size_t)g * G.stride;
+  std::vector<int32_t> sb((size_t)G.n_sb), pb((size_t)G.n_pb), so((size_t)G.n_pb), stv((size_t)std::max(1, G.n_st));
+  if (hipMemcpy(sb.data(), region + G.sb_off, sb.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(pb.data(), region + G.pb_off, pb.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(so.data(), region + G.so_off, so.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (G.n_st > 0 && hipMemcpy(stv.data(), region + G.st_off, (size_t)G.n_st * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const std::vector<int32_t>& sl = ps.planner.slots();
+  const int32_t n = G.n_pb - 1;
+  if (counts4) { counts4[0] = G.n_sb; counts4[1] = n; counts4[2] = G.n_st; counts4[3] = G.total_bits[g]; }
+  for (int32_t k = 0; k < G.n_sb && k < cap_slots; k++) slot_base[k] = sb[(size_t)k];
+  for (int32_t k = 0; k <= n && k <= cap_paths && cap_paths > 0; k++) { path_base[k] = pb[(size_t)k]; start_off[k] = so[(size_t)k]; }
+  for (int32_t k = 0; k < n && k < cap_paths && k < (int32_t)sl.size(); k++) slots[k] = sl[(size_t)k];
+  for (int32_t k = 0; k < G.n_st && k < cap_starts; k++) starts[k] = stv[(size_t)k];
+  return n;
+}
+
 int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* c, int rs, int mate, int32_t wid, int32_t* out, int32_t cap) {
   MULTI_SHARD0(c);
   ShortMate* m = mate_of(c, rs, mate);

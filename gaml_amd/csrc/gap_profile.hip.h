@@ -9,10 +9,17 @@
 // the "general" flag that follows from it (occ_prepack: min_pos > 32767) moves; ranks and path slots stay. What differs
 // between two candidates is the `shift` word of the occurrences of the edited path behind the gap -- in the 12-byte
 // table entries and in the lists of windows that occur several times -- and the thresholds that follow from 2T.
+// A set with a coverage penalty has its coverage layout [slot_base | path_base | start_off | starts] (paired_cov_build) as
+// well: a path keeps bits(len) = ((len + 64 + 31) / 32) * 32 bits, so the edited path's region grows by dbits = bits(len + d)
+// - bits(len) (a multiple of 32, not d), every region behind it moves by dbits, and the edited path's contig starts behind
+// the gap move by d. Marks need nothing new: a lane marks at slot_base[slot] + shift + position. Such a set takes the device
+// route only where the context asks for it (gaml_hip_set_gap_penalty_device / GAML_HIP_GAP_PENALTY=device).
 //
-//   gap_tables_kernel     region g of an arena slot := the resident tables, those shift words + (lens[g] - base)
+//   gap_tables_kernel     region g of an arena slot := the resident tables, those shift words + (lens[g] - base); for a
+//                         penalised set a third grid row: region g's coverage layout := the resident one by the rules above
 //   gap_profile_device    plan the set once with the base length, then per pass of up to kMaxSets lengths: thresholds
-//                         through the BAR, gap_tables_kernel, paired_score_multi_kernel (launch_paired_multi, unchanged);
+//                         through the BAR, gap_tables_kernel, paired_score_multi_kernel (launch_paired_multi, unchanged;
+//                         a penalised set: every length a PairedPrep with its own total_bits, bitmaps and sweep as a batch's);
 //                         scope, wait and results of a pass are the batch routes' (MultiPass, multi_wait, multi_collect:
 //                         paired_batch.hip.h), the copy geometry theirs too (paired_tab_geometry)
 //   gap_profile_fallback  the same lengths as path sets of gaml_hip_calc_prob_batch / collective gaml_hip_calc_prob calls
@@ -35,6 +42,15 @@ struct GapTabArgs {
   int delta[kMaxSets];   // set g: its gap length minus the base length
   unsigned char* chg[2]; // per mate: MultiSets::chg of this launch (one byte per table entry)
   size_t chg_bytes[2];   // multiples of 16, >= n_occ
+  // a set with a coverage penalty (cov != 0; grid row 2): the layout [slot_base | path_base | start_off | starts] of the set
+  // with the base length sits in the resident copy, every region gets its own at the same offsets
+  int cov;
+  size_t off_sb, off_pb, off_so, off_st;  // from `base` / from a region's start
+  int n_sb, n_pb, n_st;  // slots; paths + 1 (path_base and start_off alike); contig starts of all paths
+  int edited;            // position of the edited path in the set
+  int edited_base;       // path_base[edited] of the base layout: a region behind it starts at a larger bit
+  int st_from, st_to;    // starts[st_from .. st_to): the edited path's contig starts behind the gap
+  int dbits[kMaxSets];   // set g: bits the edited path's region grows by (a multiple of 32; not delta)
 };
 
 // a direct entry {lo = shift, hi = min_pos:16 | path:15 | general:1, rank} of the edited path behind the gap
@@ -44,12 +60,34 @@ __device__ __forceinline__ bool gap_direct_behind(unsigned lo, unsigned hi, int 
   return (int)((hi >> 16) & 0x7fffu) == slot && rank >= first_rank;
 }
 
-__global__ __launch_bounds__(1024) void gap_tables_kernel(GapTabArgs a) {  // grid (sets of this launch + 1, 2 mates)
+// grid (sets of this launch + 1, 2 mates), and a third row when the set carries a coverage penalty
+__global__ __launch_bounds__(1024) void gap_tables_kernel(GapTabArgs a) {
+  if (blockIdx.y == 2) {
+    // region g's coverage layout (paired_cov_build of the set planned with lens[g]): the edited path's region grows by
+    // dbits, every region behind it moves by as much, the edited path's contig starts behind the gap move by delta
+    const int g = (int)blockIdx.x;
+    if (g >= a.n_sets) return;
+    const int delta = a.delta[g], dbits = a.dbits[g];
+    char* region = a.regions + (size_t)g * a.stride;
+    const int* src_sb = (const int*)(a.base + a.off_sb);
+    const int* src_pb = (const int*)(a.base + a.off_pb);
+    const int* src_so = (const int*)(a.base + a.off_so);
+    const int* src_st = (const int*)(a.base + a.off_st);
+    int* dst_sb = (int*)(region + a.off_sb);
+    int* dst_pb = (int*)(region + a.off_pb);
+    int* dst_so = (int*)(region + a.off_so);
+    int* dst_st = (int*)(region + a.off_st);
+    for (int j = (int)threadIdx.x; j < a.n_sb; j += (int)blockDim.x) { const int v = src_sb[j]; dst_sb[j] = v + (v > a.edited_base ? dbits : 0); }
+    for (int j = (int)threadIdx.x; j < a.n_pb; j += (int)blockDim.x) { dst_pb[j] = src_pb[j] + (j > a.edited ? dbits : 0); dst_so[j] = src_so[j]; }
+    for (int j = (int)threadIdx.x; j < a.n_st; j += (int)blockDim.x) dst_st[j] = src_st[j] + (j >= a.st_from && j < a.st_to ? delta : 0);
+    return;
+  }
   const int mt = (int)blockIdx.y;
   const int* src_occ = (const int*)(a.base + a.off_occ[mt]);
   const int* src_lo = (const int*)(a.base + a.off_lo[mt]);
   const int4* src_m = (const int4*)(a.base + a.off_m[mt]);
   if ((int)blockIdx.x == a.n_sets) {
+    if (a.cov) return;  // (a penalised launch runs without the capture: launch_paired_multi)
     // which entries differ between the sets of this launch: every shifted one, in every set behind the first (the
     // lengths of a launch are distinct; equal ones would only resolve a pair again). A thread writes four entries' bytes.
     const unsigned bits = (0xfeu & ((1u << a.n_sets) - 1u));
@@ -105,9 +143,10 @@ bool gap_device_capable(const gaml_hip_ctx* c) {
   if (c->multi || c->comm || c->device < 0 || c->world != 1 || c->peers != 1) return false;
   if (KNOB(c, GAP_FALLBACK) == 1) return false;  // the fallback route (A/B, tests)
   if (!c->direct_write || KNOB(c, UPLOAD_ROUTE) != 0 || KNOB(c, NO_RESIDENT_TABLES) != 0) return false;
-  // a set with a coverage penalty: gap_tables_kernel moves table entries, not the set's coverage layout -- such a context
-  // searches through the fallback (whose multi-length steps are batches, one pass each)
-  for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0) return false;
+  // a set with a coverage penalty: gap_tables_kernel derives every length's coverage layout too, where the context asks for it
+  // (gaml_hip_set_gap_penalty_device); otherwise such a context searches through the fallback (whose multi-length steps are
+  // batches, one pass each)
+  if (!c->gap_penalty_device) for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0) return false;
   return batch_fast_capable(c);
 }
 
@@ -119,11 +158,31 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
   const size_t nps = c->paireds.size();
   HIP_TRY(c, hipSetDevice(c->device));
   for (auto& ps : c->paireds) paired_images_refresh(*ps);
+  // penalised sets: a path keeps bits(len) bits of the coverage bitmap (paired_cov_build), so a length moves the set's
+  // total_bits by dbits = bits(len + d) - bits(len) of the edited path; every length's total must fit int32
+  bool any_cov = false;
+  for (auto& ps : c->paireds) any_cov = any_cov || ps->cfg.penalty_constant > 0;
+  auto cov_bits_of = [](int64_t len) { return ((len + 64 + 31) / 32) * 32; };
+  int64_t edited_len = 0, base_bits = 0;
+  int starts_before = 1;  // contig starts of the edited path that are not behind the gap: the path's own and one per gap in front
+  if (any_cov) {
+    for (int32_t k = 0; k < n_paths; k++) {
+      int64_t len = 0;
+      for (int64_t q = c->gap_offs[k]; q < c->gap_offs[k + 1]; q++) len += c->gap_flat[q] < 0 ? -(int64_t)c->gap_flat[q] : c->g.len(c->gap_flat[q]);
+      if (k == path_id) edited_len = len;
+      base_bits += cov_bits_of(len);
+    }
+    for (int64_t q = c->gap_offs[path_id]; q < c->gap_offs[path_id] + gap_pos; q++) if (c->gap_flat[q] < 0) starts_before++;
+    for (int32_t k = 0; k < n_lens; k++)
+      if (base_bits + cov_bits_of(edited_len + (lens[k] - base_len)) - cov_bits_of(edited_len) > 0x7fffffffLL) return 1;  // (the fallback says what is wrong)
+    for (auto& ps : c->paireds) ps->batch_bad.clear();  // per length of this profile (multi_collect)
+  }
   struct PerSet {
     int slot = 0; char* wp = nullptr; size_t stride = 0;
     PairedLayout L; std::vector<PairedLayout> Ls; std::vector<PairedPrep> prep;
     size_t bw[2] = {0, 0}, chg_bytes[2] = {0, 0};
     int path_slot = 0, first_rank[2] = {0, 0};
+    bool cov = false; int32_t base_bits = 0; int st_from = 0, st_to = 0, edited_base = 0;
   };
   std::vector<PerSet> per(nps);
   const int chunk = std::min<int32_t>(kMaxSets, n_lens);
@@ -143,8 +202,12 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     if (int e = prepare_paired_tables_host(c, ps, r.prep[0])) return e;
     if (int e = paired_sync_tables(c, ps, st)) return e;
     PairedSet::Persist& P = ps.persist;
-    // the resident copy follows the images: now the set with the base length
-    if (paired_persist_stale(ps)) { if (int e = paired_persist_update(c, ps, (double)(2 * (tl0 == 0 ? 1 : tl0)), st)) return e; }
+    // the resident copy follows the images: now the set with the base length -- of a penalised set with its coverage layout
+    r.cov = ps.cfg.penalty_constant > 0;
+    PairedLayout cov_L;
+    memset(&cov_L, 0, sizeof(cov_L));
+    if (r.cov) { if (int e = paired_persist_update(c, ps, (double)(2 * (tl0 == 0 ? 1 : tl0)), st, &r.prep[0], &cov_L)) return e; }
+    else if (paired_persist_stale(ps)) { if (int e = paired_persist_update(c, ps, (double)(2 * (tl0 == 0 ? 1 : tl0)), st)) return e; }
     if ((size_t)path_id >= ps.planner.slots().size()) return fail(c, GAML_HIP_ESTATE, "gap profile: the planner does not hold the path set");
     r.path_slot = ps.planner.slots()[(size_t)path_id];
     const PathMemo& pm = ps.planner.memo(ps.planner.ids()[(size_t)path_id]);
@@ -158,6 +221,15 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     }
     r.stride = align16(P.bytes);
     r.L = paired_persist_layout(P);
+    if (r.cov) {
+      const PairedPrep& p0 = r.prep[0];
+      if ((size_t)path_id + 1 >= p0.path_base.size() || (int64_t)p0.total_bits != base_bits) return fail(c, GAML_HIP_ESTATE, "gap profile: the coverage layout is not the path set's");
+      r.L.sb_off = cov_L.sb_off; r.L.pb_off = cov_L.pb_off; r.L.so_off = cov_L.so_off; r.L.st_off = cov_L.st_off;  // (every region: at the resident copy's offsets)
+      r.base_bits = p0.total_bits;
+      r.edited_base = p0.path_base[(size_t)path_id];
+      r.st_from = std::min(p0.start_off[(size_t)path_id] + starts_before, p0.start_off[(size_t)path_id + 1]);
+      r.st_to = p0.start_off[(size_t)path_id + 1];
+    }
     r.Ls.assign((size_t)chunk, r.L);
     { const PairedPrep one = r.prep[0]; r.prep.assign((size_t)chunk, one); }  // every length: the same windows, lists and records
     if (int e = arena_acquire(c, ps.arena, r.stride * (size_t)chunk + r.chg_bytes[0] + r.chg_bytes[1], st, &r.slot, &r.wp)) return e;
@@ -186,13 +258,27 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
       ta.slot = r.path_slot;
       ta.n_sets = n;
       for (int k = 0; k < n; k++) ta.delta[k] = lens[done + k] - base_len;
-      hipLaunchKernelGGL(gap_tables_kernel, dim3((unsigned)n + 1, 2), dim3(1024), 0, st, ta);
+      if (r.cov) {
+        const PairedPrep& p0 = r.prep[0];
+        ta.cov = 1;
+        ta.off_sb = r.L.sb_off; ta.off_pb = r.L.pb_off; ta.off_so = r.L.so_off; ta.off_st = r.L.st_off;
+        ta.n_sb = (int)p0.slot_base.size(); ta.n_pb = (int)p0.path_base.size(); ta.n_st = (int)p0.starts.size();
+        ta.edited = path_id; ta.edited_base = r.edited_base;
+        ta.st_from = r.st_from; ta.st_to = r.st_to;
+        for (int k = 0; k < n; k++) {
+          ta.dbits[k] = (int)(cov_bits_of(edited_len + ta.delta[k]) - cov_bits_of(edited_len));
+          r.prep[(size_t)k].total_bits = r.base_bits + ta.dbits[k];  // (launch_paired_multi sizes the bitmaps and the sweep from it)
+        }
+        ps.gap_cov = PairedSet::GapCov{r.slot, n, r.stride, r.L.sb_off, r.L.pb_off, r.L.so_off, r.L.st_off, ta.n_sb, ta.n_pb, ta.n_st, {0}};
+        for (int k = 0; k < n; k++) ps.gap_cov.total_bits[k] = r.prep[(size_t)k].total_bits;
+      }
+      hipLaunchKernelGGL(gap_tables_kernel, dim3((unsigned)n + 1, r.cov ? 3 : 2), dim3(1024), 0, st, ta);
       HIP_TRY(c, hipGetLastError());
       const unsigned char* chg[2] = {ta.chg[0], ta.chg[1]};
       if (int e = launch_paired_multi(c, ps, 0, n, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.dev[r.slot], r.stride, st, chg)) return e;
     }
     if (int e = multi_wait(c)) return e;
-    multi_collect(c, n, part.data(), false);  // (no penalised set comes this way: gap_device_capable)
+    multi_collect(c, n, part.data(), any_cov);
     for (int k = 0; k < n; k++) {
       const int32_t at = done + k;
       if (int e = combine(c, part.data() + (size_t)k * 4 * ns, &probs_out[at], zeros_out ? zeros_out + (size_t)at * 2 * ns : nullptr, tls[k])) return e;
@@ -324,6 +410,13 @@ int gaml_hip_gap_profile(gaml_hip_ctx* c, const int32_t* paths, const int64_t* o
   }
   return gap_profile_impl(c, paths, offs, n_paths, path_id, gap_pos, n_lens > 0 ? lens[0] : 1, lens, n_lens, probs_out, zeros_out, total_lens_out);
 }
+
+int gaml_hip_set_gap_penalty_device(gaml_hip_ctx* c, int32_t on) {
+  if (!c) return GAML_HIP_EINVAL;
+  c->gap_penalty_device = on != 0;  // (a context the device route never serves only keeps the flag: gap_device_capable)
+  return GAML_HIP_OK;
+}
+int gaml_hip_get_gap_penalty_device(const gaml_hip_ctx* c) { return c && c->gap_penalty_device ? 1 : 0; }
 
 int gaml_hip_gap_stats(gaml_hip_ctx* c, int64_t* out4) {
   if (!c || !out4) return GAML_HIP_EINVAL;

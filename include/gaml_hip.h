@@ -335,7 +335,10 @@ int64_t gaml_hip_advice_candidates(gaml_hip_ctx* ctx, int readset, const int32_t
  *   coverage penalty on a large-BAR device plans the set once, with lens[0], derives every other length's tables from
  *   the resident ones on the device and scores up to 8 lengths per pass over the records. Every other context (other
  *   kinds of read sets, a penalty, no memo, several devices, rank-per-process -- there the call is collective) runs the
- *   lengths through gaml_hip_calc_prob_batch / gaml_hip_calc_prob: same values. GAML_HIP_EINVAL: path_id or gap_pos
+ *   lengths through gaml_hip_calc_prob_batch / gaml_hip_calc_prob: same values. A set with a coverage penalty takes the
+ *   device route too once gaml_hip_set_gap_penalty_device says so (every length's coverage layout is then derived on the
+ *   device beside its tables; a length whose bitmap would not fit int32 bits sends the call to the fallback).
+ *   GAML_HIP_EINVAL: path_id or gap_pos
  *   out of range, an entry that is not a gap, a length < 1, n_lens < 0, a total length beyond int32. n_lens == 0 does
  *   nothing. Afterwards the library's tables describe the set with lens[0].
  * gaml_hip_fix_gap_length: FixGapLength(paths, path_id, gap_pos, prob_calc, prev_len) -- *len_out is the length the
@@ -346,7 +349,11 @@ int64_t gaml_hip_advice_candidates(gaml_hip_ctx* ctx, int readset, const int32_t
  *   not one blocking call per evaluation; where the profile takes its fallback nothing is computed ahead.
  *   GAML_HIP_EINVAL also when the search reaches a length whose total would not fit int32.
  * gaml_hip_gap_stats: cumulative {profile calls (the search's included), lengths scored on the device route, lengths
- *   scored on the fallback, device passes}. */
+ *   scored on the fallback, device passes}.
+ * gaml_hip_set_gap_penalty_device / gaml_hip_get_gap_penalty_device: may paired sets with a coverage penalty take the
+ *   device route (1) or not (0, the default). Per context, any kind of context: one the device route never serves only
+ *   keeps the flag. A new context starts with 1 when the environment holds GAML_HIP_GAP_PENALTY=device. Same values on
+ *   both routes. */
 int gaml_hip_gap_profile(gaml_hip_ctx* ctx, const int32_t* paths, const int64_t* path_offs, int32_t n_paths,
                          int32_t path_id, int32_t gap_pos, const int32_t* lens, int32_t n_lens,
                          double* probs_out, int32_t* zeros_out /* n_lens * 2 * num_readsets, may be NULL */,
@@ -355,6 +362,8 @@ int gaml_hip_fix_gap_length(gaml_hip_ctx* ctx, const int32_t* paths, const int64
                             int32_t path_id, int32_t gap_pos, int32_t* len_out,
                             int32_t* trace_lens, double* trace_probs, int32_t trace_cap, int32_t* n_trace_out);
 int gaml_hip_gap_stats(gaml_hip_ctx* ctx, int64_t* out4);
+int gaml_hip_set_gap_penalty_device(gaml_hip_ctx* ctx, int32_t on);
+int gaml_hip_get_gap_penalty_device(const gaml_hip_ctx* ctx);
 
 /* ---- introspection (tests, bench, logging) ----------------------------------------- */
 int gaml_hip_num_readsets(const gaml_hip_ctx* ctx);

@@ -56,6 +56,13 @@ int64_t gaml_hip_debug_table_occurrences(gaml_hip_ctx* ctx, int readset, int mat
  * number of paths, -1 when the set has no penalty or nothing was prepared. Works on a host-only context. */
 int32_t gaml_hip_debug_cov_layout(gaml_hip_ctx* ctx, int readset, int32_t* slot_base, int32_t cap_slots, int32_t* path_base, int32_t* start_off,
                                   int32_t* slots, int32_t cap_paths, int32_t* starts, int32_t cap_starts, int32_t* counts4);
+/* The same of region g of the last pass of a gap profile that took the device route (gaml_hip_gap_profile with
+ * gaml_hip_set_gap_penalty_device on): what gap_tables_kernel derived for the g-th length of that pass, copied back from the
+ * arena; counts4[3] is the total the host sized that length's bitmap and sweep with. Arguments and format as above. Returns
+ * -1 when the set has no penalty, no such pass ran, the pass had no region g, or the context has no device. Call it before
+ * the next evaluation re-uses the arena slot. */
+int32_t gaml_hip_debug_gap_cov_layout(gaml_hip_ctx* ctx, int readset, int g, int32_t* slot_base, int32_t cap_slots, int32_t* path_base,
+                                      int32_t* start_off, int32_t* slots, int32_t cap_paths, int32_t* starts, int32_t cap_starts, int32_t* counts4);
 /* node ids of a cached window (by id); returns its length, -1 if the id is unknown */
 int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int32_t window_id, int32_t* out, int32_t cap);
 /* ---- tuning ------------------------------------------------------------------------------------- */

@@ -6,12 +6,20 @@
   b  gaml_hip_fix_gap_length on a context with Knob.GAP_FALLBACK: the fallback route, one batch call per step of the search
   c  gaml_hip_fix_gap_length on the device route: passes of up to 8 lengths, tables derived on the device
 
+With --penalty the read set carries the example configuration's coverage penalty (tools/penalty_probe.py: KW), and two more
+ways tell the routes of such a set apart:
+
+  f  gaml_hip_fix_gap_length with the context's gap_penalty_device flag off: the fallback a penalised context takes by
+     default (what every library before the flag does: run this way alone under GAML_HIP_LIB=<older build> for that leg)
+  p  the same with the flag on: the device route, every length's coverage layout derived on the device
+
 The path set is the genome walk cut into contigs of `--contig` nodes; a site replaces one inner node of a contig by a gap
 whose starting length is the node's length, a third of it, or twice it + 5 (in turn). One search per site and way,
 the ways alternated site by site, the whole round `--reps` times: per way and round the median and p90 per search; the
 figure to compare is c's median against the spread of a's medians over the rounds. Every way must find the same length.
 
 Usage: python tools/gap_probe.py --workload cfg3j [--sites 200] [--reps 5] [--ways abc]
+       python tools/gap_probe.py --workload cfg3j --penalty --ways fp [--tag NAME]
        rocprofv3 --kernel-trace --stats -d DIR -- python tools/gap_probe.py --workload cfg3j --ways c --reps 1
 """
 from __future__ import annotations
@@ -81,7 +89,10 @@ def main():
     ap.add_argument("--contig", type=int, default=8)
     ap.add_argument("--ways", default="abc")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--penalty", action="store_true", help="the example configuration's coverage penalty on the read set")
+    ap.add_argument("--tag", default="")
     a = ap.parse_args()
+    kw = dict(penalty_constant=0.00013, penalty_step=3000.0, min_prob_start=-80.0) if a.penalty else {}  # (tools/penalty_probe.py: KW)
     wl = synth.WORKLOADS[a.workload]
     genome, g = wl.build()
     pr = synth.make_paired_reads(genome, wl.n_pairs, wl.read_len, wl.insert_mean, wl.insert_std, wl.err, wl.seed)
@@ -94,9 +105,11 @@ def main():
     for name in a.ways:
         ctx = api.Context(device=a.device)
         ctx.set_graph(*g.packed())
-        ctx.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std), *r1, *r2)
+        ctx.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std, **kw), *r1, *r2)
         if name == "b":
             ctx.debug_set_knob(api.Knob.GAP_FALLBACK, 1)
+        if name == "p" or (name == "c" and a.penalty):
+            ctx.set_gap_penalty_device(True)
         ways.append(Way(name, ctx))
     # one flat path set per site (the node at the site replaced by the gap), built before anything is timed
     fps = []
@@ -114,7 +127,7 @@ def main():
             w.search(fp, at, pid, pos, start)
         w.us, w.evals, w.passes, w.lengths = [], [], [], []
 
-    res = {"workload": a.workload, "pairs": wl.n_pairs, "paths": len(paths), "nodes": int(offs[-1]), "sites": a.sites, "reps": a.reps, "ways": {}}
+    res = {"tag": a.tag, "lib": os.environ.get("GAML_HIP_LIB", ""), "penalty": kw, "workload": a.workload, "pairs": wl.n_pairs, "paths": len(paths), "nodes": int(offs[-1]), "sites": a.sites, "reps": a.reps, "ways": {}}
     rounds = {w.name: [] for w in ways}
     for rep in range(a.reps):
         for w in ways:
@@ -137,6 +150,10 @@ def main():
         }
     res["final_length_median"] = float(np.median(ways[0].lengths))
     res["searches_that_move"] = int(sum(1 for n in ways[0].evals[:a.sites] if n > 3))
+    if "f" in res["ways"] and "p" in res["ways"]:
+        F, P = res["ways"]["f"], res["ways"]["p"]
+        res["p_below_f_by_us"] = round(F["median_us"] - P["median_us"], 1)
+        res["p_below_f_by_more_than_the_rounds_differ"] = bool(F["median_us"] - P["median_us"] > max(F["median_spread_us"], P["median_spread_us"]))
     if "a" in res["ways"] and "c" in res["ways"]:
         A, Cw = res["ways"]["a"], res["ways"]["c"]
         res["c_below_a_by_us"] = round(A["median_us"] - Cw["median_us"], 1)

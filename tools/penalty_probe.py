@@ -5,7 +5,8 @@ cfg3j as bench.py's `jumping` block sets it up): one JSON line.
      median, p90 and max, and the median of gaml_hip_last_phases -- the calls that share most paths with their predecessor
   b  the 8 rotating unrelated path sets of bench.py (every call a whole-set call), 400 calls
   c  200 gaml_hip_fix_gap_length searches at the sites tools/gap_probe.py uses (a penalised set: the fallback route, one
-     blocking call per evaluation; its steps of 2-3 lengths are batches)
+     blocking call per evaluation; its steps of 2-3 lengths are batches -- or, with --gap-penalty-device, the device route:
+     passes of up to 8 lengths, every length's coverage layout derived on the device)
   d  gaml_hip_calc_prob_batch: 200 batches of 8 single-edit candidates of the current assembly (synth.sa_move, 60 % of the
      batches adopt one candidate), 100 batches of the 8 unrelated path sets of part b, and 100 batches each of the first
      2, 3 and 4 candidates (the sizes of the gap fallback's steps): per batch and per candidate the median, p90 and max
@@ -64,6 +65,7 @@ def main():
     ap.add_argument("--batches", type=int, default=200)
     ap.add_argument("--tag", default="")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--gap-penalty-device", action="store_true", help="part c on the gap profile's device route (Context.set_gap_penalty_device)")
     a = ap.parse_args()
     wl = synth.WORKLOADS["cfg3j"]
     genome, g = wl.build()
@@ -74,9 +76,12 @@ def main():
         c = api.Context(device=a.device)
         c.set_graph(*g.packed())
         c.add_paired(api.paired_cfg(wl.insert_mean, wl.insert_std, **KW), *r1, *r2)
+        if a.gap_penalty_device:
+            c.set_gap_penalty_device(True)
         return c
 
-    res = {"tag": a.tag, "lib": os.environ.get("GAML_HIP_LIB", ""), "version": api.version(), "workload": wl.name, "pairs": wl.n_pairs, "config": KW}
+    res = {"tag": a.tag, "lib": os.environ.get("GAML_HIP_LIB", ""), "version": api.version(), "workload": wl.name, "pairs": wl.n_pairs, "config": KW,
+           "gap_penalty_device": bool(a.gap_penalty_device)}
     gc.disable()
     if "a" in a.parts:
         start, seq = synth.sa_sequence(g, a.steps)
