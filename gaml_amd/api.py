@@ -330,6 +330,8 @@ def _load():
         L.gaml_hip_get_gap_penalty_device.argtypes = [vp]
     if hasattr(L, "gaml_hip_debug_timeline"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_debug_timeline.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64]
+    if hasattr(L, "gaml_hip_pacbio_stats"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_pacbio_stats.argtypes = [vp, C.c_int, _i64p]
     L.gaml_hip_last_phases.argtypes = [vp, _f64p]
     L.gaml_hip_table_stats.argtypes = [vp, C.c_int, _i64p]
     L.gaml_hip_aligner_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -902,6 +904,15 @@ class Context:
         return {"full_rebuilds": int(out[0]), "delta_updates": int(out[1]), "dirty_pairs": int(out[2]), "worker_rebuilds": int(out[3]), "side_stream_rebuilds": int(out[3]),
                 "batches_patched": int(out[4]), "batches_full": int(out[5]), "records_left_out": [int(out[6]), int(out[7])], "delta_records_left_out": int(out[8]),
                 "static_index_pairs": int(out[9])}
+
+    def pacbio_stats(self, rs):
+        """{subwalks, records, misses, multi_launches} of a PacBio set's record cache (gaml_hip_pacbio_stats): cached sub-walks,
+        cached records, sub-walk lookups that found nothing cached so far, batch chunks scored in one multi-set launch."""
+        if not hasattr(_lib, "gaml_hip_pacbio_stats"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_pacbio_stats")
+        out = np.zeros(4, np.int64)
+        self._check(_lib.gaml_hip_pacbio_stats(self._h, rs, out))
+        return {"subwalks": int(out[0]), "records": int(out[1]), "misses": int(out[2]), "multi_launches": int(out[3])}
 
     def aligner_stats(self):
         w, k, us = C.c_int64(), C.c_int64(), C.c_double()

@@ -437,6 +437,22 @@ struct PbSweepDev {
   }
 };
 
+// what a path contributes to a PacBio evaluation (pacbio_enumerate): its cached sub-walks in the order the reference
+// meets them (graph.cc:2438-2454), each with the path coordinate it starts at, and the lookups that found nothing
+struct PbHit { int32_t walk, begin; };
+struct PbEnum { std::vector<PbHit> hits; int64_t misses = 0; int32_t len = 0; };
+
+// a PacBio set's side of gaml_hip_calc_prob_batch (pacbio_batch.hip.h)
+struct PbMulti {
+  std::unordered_map<Walk, PbEnum, WalkHasher> memo;  // by normalised path; holds for one state of the record cache
+  uint64_t memo_generation = ~0ull;
+  DevBuf count;     // [sub-walk][kMaxSets] occurrence counts of the chunk's path sets
+  DevBuf part_sum, part_zero, ticket;  // per set and block; a ticket of its own (pacbio_score_multi_kernel)
+  PinBuf out;       // {sum, floored, 0, reads} per set, written by the last block
+  int64_t launches = 0;
+  void release() { count.release(); part_sum.release(); part_zero.release(); ticket.release(); out.release(); }
+};
+
 struct PacbioSet {
   gaml_single_cfg cfg;
   int64_t n_global = 0, lo = 0, hi = 0;
@@ -452,6 +468,7 @@ struct PacbioSet {
   int64_t last_bad_bases = 0;
   Staging stage;
   PbSweepDev sweep;
+  PbMulti multi;
   // cache-miss side (SAM ingestion): bases of this shard's reads and the name -> global id map
   bool have_reads = false;
   std::string bases;

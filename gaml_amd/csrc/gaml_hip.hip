@@ -233,6 +233,7 @@ namespace {
 
 #include "single_launch.hip.h"
 #include "pacbio_launch.hip.h"
+#include "pacbio_batch.hip.h"
 #include "aligner_launch.hip.h"
 std::vector<ShortMate*> filter_mates(gaml_hip_ctx* c) {  // mates whose windows feed a position filter, in handle order
   std::vector<ShortMate*> v;
@@ -520,7 +521,7 @@ void gaml_hip_destroy(gaml_hip_ctx* c) {
       s->red.release(); s->adv.release();
     }
     for (auto& s : c->pacbios) { s->d_lens.release(); s->rec_off.release(); s->rec_walk.release(); s->rec_logp.release(); s->walk_count.release(); s->logprobs.release(); s->red.release(); drop_stage(s->stage);
-      s->d_bases.release(); s->dp.release(); s->sweep.release(); }
+      s->d_bases.release(); s->dp.release(); s->sweep.release(); s->multi.release(); }
     c->packed.release(); c->packed_host.release(); c->batch_dev.release(); c->batch_host.release(); c->aln_scratch.release();
     c->aln_small[0].release(); c->aln_small[1].release(); c->fetch_host.release(); c->warm_buf.release();
     for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1083,6 +1084,8 @@ int gaml_hip_calc_partials(gaml_hip_ctx* c, const int32_t* paths, const int64_t*
   HIP_TRY(c, hipHostGetDevicePointer(&dres, c->packed_host.p, 0));
   c->host_results = true;
   c->occ_route = true;
+  std::vector<int64_t> pb_misses;  // (an evaluation whose launches run twice, below, looks its sub-walks up twice: counted once)
+  for (auto& pb : c->pacbios) pb_misses.push_back(pb->misses);
   int e = evaluate(c, paths, offs, n_paths, dres, c->stream, total_len_out);
   c->occ_route = false;
   c->host_results = false;
@@ -1101,6 +1104,7 @@ int gaml_hip_calc_partials(gaml_hip_ctx* c, const int32_t* paths, const int64_t*
     redo = true;
   }
   if (!redo) return GAML_HIP_OK;
+  for (size_t i = 0; i < c->pacbios.size(); i++) c->pacbios[i]->misses = pb_misses[i];
   c->host_results = true;
   c->pending_open = true;
   e = eval_finish(c, dres, c->stream);
@@ -1431,6 +1435,16 @@ int gaml_hip_table_stats(gaml_hip_ctx* c, int rs, int64_t* out10) {
   out8[4] = s.batches_patched; out8[5] = s.batches_full;
   out8[6] = s.pt.dropped_records[0]; out8[7] = s.pt.dropped_records[1];
   out10[8] = s.delta_left_out; out10[9] = s.pt.n0a;
+  return GAML_HIP_OK;
+}
+
+int gaml_hip_pacbio_stats(gaml_hip_ctx* c, int rs, int64_t* out4) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 2 || !out4) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const PacbioSet& s = *c->pacbios[c->handles[rs].idx];
+  int64_t nrec = 0;
+  for (auto& v : s.recs) nrec += (int64_t)v.size();
+  out4[0] = (int64_t)s.recs.size(); out4[1] = nrec; out4[2] = s.misses; out4[3] = s.multi.launches;
   return GAML_HIP_OK;
 }
 

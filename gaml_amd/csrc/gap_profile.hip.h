@@ -147,6 +147,7 @@ bool gap_device_capable(const gaml_hip_ctx* c) {
   // (gaml_hip_set_gap_penalty_device); otherwise such a context searches through the fallback (whose multi-length steps are
   // batches, one pass each)
   if (!c->gap_penalty_device) for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0) return false;
+  for (auto& h : c->handles) if (h.kind != 1) return false;  // (the batch routes take PacBio sets along; the tables this route derives are the paired sets')
   return batch_fast_capable(c);
 }
 

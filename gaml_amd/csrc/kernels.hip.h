@@ -2288,6 +2288,126 @@ __global__ __launch_bounds__(kBlock) void pacbio_score_kernel(PacbioArgs a) {
   grid_finish(lsum, zeros, blockIdx.x, gridDim.x, a.part_sum, a.part_zero, a.ticket, a.out, a.bad_bases, a.n_reads, sh_s, sh_z);
 }
 
+// The same for up to kMaxSets path sets in one pass over the records (gaml_hip_calc_prob_batch, pacbio_batch.hip.h): a
+// record's sub-walk id and log probability are loaded once, the sets' occurrence counts of that sub-walk stand side by
+// side in `counts` (32 bytes per sub-walk: two 16-byte loads). Same grid, same read-to-wave mapping, same fold order and
+// the same finishing arithmetic as pacbio_score_kernel, per set: every set's four partials are the bits a call of its own
+// would give. The per-set values live in registers: every loop over the sets is unrolled over the compile-time kMaxSets
+// with the guard s < n_sets, no array is indexed at run time.
+struct PacbioMultiArgs {
+  const int* rec_off; const int* rec_walk; const double* rec_logp;
+  const int* counts;         // [sub-walk][kMaxSets]; columns >= n_sets hold 0
+  const int* lens;
+  double floor_a, floor_b;
+  int n, n_sets;
+  double* logprobs;          // out: per-read log probability under the LAST set (what sequential calls leave there)
+  double* part_sum; int* part_zero;  // set s, block b: [s * part_stride + b]
+  int part_stride;
+  unsigned* ticket;          // kTicketWords, one ticket for all sets
+  double* out;               // set s: out[4 s ..] = {sum, floored, 0, reads}
+  double n_reads;
+};
+
+__global__ __launch_bounds__(kBlock) void pacbio_score_multi_kernel(PacbioMultiArgs a) {
+  __shared__ double sh_s[kMaxSets][kBlock / 64];
+  __shared__ int sh_z[kMaxSets][kBlock / 64];
+  __shared__ bool is_last;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wave_global = (blockIdx.x * kBlock + threadIdx.x) >> 6;
+  const int n_waves = (gridDim.x * kBlock) >> 6;
+  double lsum[kMaxSets];
+  int zeros[kMaxSets];
+#pragma unroll
+  for (int s = 0; s < kMaxSets; s++) { lsum[s] = 0.0; zeros[s] = 0; }
+  for (int i = wave_global; i < a.n; i += n_waves) {
+    const int b = a.rec_off[i], e = a.rec_off[i + 1];
+    double v[kMaxSets];
+#pragma unroll
+    for (int s = 0; s < kMaxSets; s++) v[s] = -__builtin_huge_val();
+    for (int k = b + lane; k < e; k += 64) {
+      const int4* cp = (const int4*)(a.counts + (size_t)a.rec_walk[k] * kMaxSets);
+      const int4 c0 = cp[0], c1 = cp[1];
+      const int cnt[kMaxSets] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+      const double lp = a.rec_logp[k];
+#pragma unroll
+      for (int s = 0; s < kMaxSets; s++)
+        if (s < a.n_sets) for (int t = 0; t < cnt[s]; t++) v[s] = lse2(v[s], lp);
+    }
+#pragma unroll
+    for (int s = 0; s < kMaxSets; s++)
+      if (s < a.n_sets) for (int off = 32; off > 0; off >>= 1) v[s] = lse2(v[s], __shfl_xor(v[s], off, 64));
+    if (lane == 0) {
+      const double floor_lp = a.floor_a + a.floor_b * (double)a.lens[i];
+#pragma unroll
+      for (int s = 0; s < kMaxSets; s++)
+        if (s < a.n_sets) {
+          double x = v[s];
+          if (s == a.n_sets - 1) a.logprobs[i] = x;
+          if (x < floor_lp) { zeros[s]++; x = floor_lp; }
+          lsum[s] += x;
+        }
+    }
+  }
+  // block_reduce per set, into rows of their own: one barrier for all sets
+#pragma unroll
+  for (int s = 0; s < kMaxSets; s++)
+    if (s < a.n_sets) {
+      for (int off = 32; off > 0; off >>= 1) {
+        lsum[s] += __shfl_down(lsum[s], off, 64);
+        zeros[s] += __shfl_down(zeros[s], off, 64);
+      }
+      if (lane == 0) { sh_s[s][wave] = lsum[s]; sh_z[s][wave] = zeros[s]; }
+    }
+  __syncthreads();
+  // grid_finish with ONE ticket for all sets (its `is_last` is one word: called once per set, thread 0 of the next call
+  // could overwrite it before a slow wave has read the previous value)
+  const int n_partials = (int)gridDim.x, my_slot = (int)blockIdx.x;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int s = 0; s < kMaxSets; s++)
+      if (s < a.n_sets) {
+        double ts = 0; int tz = 0;
+        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
+        __hip_atomic_store(&a.part_sum[(size_t)s * a.part_stride + my_slot], ts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&a.part_zero[(size_t)s * a.part_stride + my_slot], tz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int g = my_slot & 15;
+    const unsigned in_group = (unsigned)((n_partials - g + 15) >> 4), groups = (unsigned)min(16, n_partials);
+    bool last = false;
+    if (__hip_atomic_fetch_add(&a.ticket[1 + g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_group - 1)
+      last = __hip_atomic_fetch_add(&a.ticket[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1;
+    is_last = last;
+  }
+  __syncthreads();
+  if (!is_last) return;
+#pragma unroll
+  for (int s = 0; s < kMaxSets; s++)
+    if (s < a.n_sets) {
+      double ts = 0; int tz = 0;
+      for (int b = threadIdx.x; b < n_partials; b += kBlock) {
+        ts += __hip_atomic_load(&a.part_sum[(size_t)s * a.part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tz += __hip_atomic_load(&a.part_zero[(size_t)s * a.part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        ts += __shfl_down(ts, off, 64);
+        tz += __shfl_down(tz, off, 64);
+      }
+      if (lane == 0) { sh_s[s][wave] = ts; sh_z[s][wave] = tz; }  // (thread 0 read the rows before the barrier above)
+    }
+  __syncthreads();
+  if (threadIdx.x < kTicketWords) __hip_atomic_store(&a.ticket[threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int s = 0; s < kMaxSets; s++)
+      if (s < a.n_sets) {
+        double ts = 0; int tz = 0;
+        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
+        a.out[4 * s] = ts; a.out[4 * s + 1] = (double)tz; a.out[4 * s + 2] = 0.0; a.out[4 * s + 3] = a.n_reads;
+      }
+  }
+}
+
 // mark the slots of delta pairs in the record tables (idempotent; runs before the scoring kernel)
 __global__ __launch_bounds__(kBlock) void mark_dirty_kernel(const int* slots, int n, unsigned long long* rec8_0, int n0, int4* inl_0,
                                                             int n01, int n_main, int4* first_0) {

@@ -108,61 +108,49 @@ int pacbio_sweep_run(gaml_hip_ctx* c, PacbioSet& s, int64_t n, int32_t n_paths, 
   return 0;
 }
 
-// PacBio read set (CalcScoreForPacbio graph.cc:3171-3261)
-// ---------------------------------------------------------------------------------------
-int launch_pacbio(gaml_hip_ctx* c, PacbioSet& s, const std::vector<Walk>& paths_in, hipStream_t st, double* out4) {
+// The sub-walks of a (normalised) path that the record cache holds, in the order the reference enumerates them
+// (GetPacbioAligments graph.cc:2412-2454): from every start the walk grows until it has passed the longest read. Each
+// hit with the path coordinate its first node starts at (the coverage sweep's shift); lookups that find nothing are
+// counted, the path's length is returned along.
+void pacbio_enumerate(const gaml_hip_ctx* c, const PacbioSet& s, const Walk& path, PbEnum& out) {
+  out.hits.clear();
+  out.misses = 0;
+  const int32_t m = (int32_t)path.size();
+  std::vector<int32_t> begins(m), ends(m);
+  int32_t len = 0;
+  for (int32_t i = 0; i < m; i++) {  // graph.cc:2412-2431 (a leading gap contributes its length)
+    begins[i] = len;
+    len += path[i] < 0 ? -path[i] : c->g.len(path[i]);
+    ends[i] = len;
+  }
+  out.len = len;
+  Walk sub;
+  for (int32_t i = 0; i < m; i++) {  // graph.cc:2438-2454
+    sub.clear();
+    for (int32_t j = i; j < m; j++) {
+      sub.push_back(path[j]);
+      auto it = s.walk_id.find(sub);
+      if (it == s.walk_id.end()) out.misses++;
+      else out.hits.push_back(PbHit{it->second, begins[i]});
+      if ((ends[j] - begins[i]) - (ends[i] - begins[i]) > s.max_len) break;
+    }
+  }
+}
+
+// what every scorer launch of the set needs on the device: the reducer, the read lengths, room for the per-read values
+int pacbio_init_dev(gaml_hip_ctx* c, PacbioSet& s) {
   const int64_t n = s.hi - s.lo;
-  if (!s.red.part_sum.p) {
-    HIP_TRY(c, s.red.init());
-    HIP_TRY(c, s.d_lens.reserve(std::max<size_t>(1, n) * sizeof(int32_t)));
-    if (n) HIP_TRY(c, hipMemcpy(s.d_lens.p, s.lens.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, s.logprobs.reserve(std::max<size_t>(1, n) * sizeof(double)));
-  }
-  // sub-walk occurrence counts + coverage events, per path (graph.cc:3183-3251)
-  std::vector<int32_t> count(s.recs.size(), 0);
-  const bool cov = s.cfg.penalty_constant > 0;
-  const bool defer = cov && c->defer_cov;  // sharded: the sweep waits for the other ranks' intervals
-  std::vector<int32_t> sweep_tl, sweep_node;  // contig lengths; node intervals {contig, begin, end, 0}
-  std::vector<PbOcc> sweep_occ;
-  int32_t path_no = -1;
-  for (Walk path : paths_in) {
-    path_no++;
-    for (auto& x : path) if (x >= 0) x = c->g.norm[x];  // NormalizePath graph.h:268-273
-    const int32_t m = (int32_t)path.size();
-    std::vector<int32_t> begins(m), ends(m);
-    int32_t len = 0;
-    for (int32_t i = 0; i < m; i++) {  // graph.cc:2412-2431 (a leading gap contributes its length)
-      begins[i] = len;
-      len += path[i] < 0 ? -path[i] : c->g.len(path[i]);
-      ends[i] = len;
-    }
-    if (cov) {
-      sweep_tl.push_back(len);
-      auto interval = [&](int32_t b, int32_t e) { sweep_node.push_back(path_no); sweep_node.push_back(b); sweep_node.push_back(e); sweep_node.push_back(0); };
-      interval(-1000, 2000);  // the events (-1000, 1), (2000, -3000) of graph.cc:3198-3199
-      int32_t pp = 0;
-      for (int32_t e : path) {
-        if (e >= 0) { const int32_t cl = c->g.len(e); if (cl > 0) interval(pp, pp + cl); pp += cl; }  // graph.cc:3202-3210
-        else pp += -e;
-      }
-    }
-    Walk sub;
-    for (int32_t i = 0; i < m; i++) {  // graph.cc:2438-2454
-      sub.clear();
-      for (int32_t j = i; j < m; j++) {
-        sub.push_back(path[j]);
-        auto it = s.walk_id.find(sub);
-        if (it == s.walk_id.end()) s.misses++;  // the reference would run BLASR here (out of scope)
-        else {
-          count[it->second]++;
-          if (cov) sweep_occ.push_back(PbOcc{it->second, begins[i], path_no, 0});  // its records' intervals (graph.cc:3214-3222)
-        }
-        if ((ends[j] - begins[i]) - (ends[i] - begins[i]) > s.max_len) break;
-      }
-    }
-  }
-  const double t_after_host = now_us();
-  // read-major CSR of the cached records (rebuilt when the cache changed)
+  if (s.red.part_sum.p) return 0;
+  HIP_TRY(c, s.red.init());
+  HIP_TRY(c, s.d_lens.reserve(std::max<size_t>(1, n) * sizeof(int32_t)));
+  if (n) HIP_TRY(c, hipMemcpy(s.d_lens.p, s.lens.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(c, s.logprobs.reserve(std::max<size_t>(1, n) * sizeof(double)));
+  return 0;
+}
+
+// read-major CSR of the cached records (rebuilt when the cache changed)
+int pacbio_sync_records(gaml_hip_ctx* c, PacbioSet& s, hipStream_t st) {
+  const int64_t n = s.hi - s.lo;
   if (s.uploaded_generation != s.generation) {
     std::vector<int32_t> off(n + 1, 0);
     for (auto& v : s.recs) for (auto& r : v) off[r.read_id + 1]++;
@@ -182,6 +170,44 @@ int launch_pacbio(gaml_hip_ctx* c, PacbioSet& s, const std::vector<Walk>& paths_
     }
     s.uploaded_generation = s.generation;
   }
+  return 0;
+}
+
+// PacBio read set (CalcScoreForPacbio graph.cc:3171-3261)
+// ---------------------------------------------------------------------------------------
+int launch_pacbio(gaml_hip_ctx* c, PacbioSet& s, const std::vector<Walk>& paths_in, hipStream_t st, double* out4) {
+  const int64_t n = s.hi - s.lo;
+  if (int e = pacbio_init_dev(c, s)) return e;
+  // sub-walk occurrence counts + coverage events, per path (graph.cc:3183-3251)
+  std::vector<int32_t> count(s.recs.size(), 0);
+  const bool cov = s.cfg.penalty_constant > 0;
+  const bool defer = cov && c->defer_cov;  // sharded: the sweep waits for the other ranks' intervals
+  std::vector<int32_t> sweep_tl, sweep_node;  // contig lengths; node intervals {contig, begin, end, 0}
+  std::vector<PbOcc> sweep_occ;
+  int32_t path_no = -1;
+  PbEnum en;
+  for (Walk path : paths_in) {
+    path_no++;
+    for (auto& x : path) if (x >= 0) x = c->g.norm[x];  // NormalizePath graph.h:268-273
+    pacbio_enumerate(c, s, path, en);
+    if (cov) {
+      sweep_tl.push_back(en.len);
+      auto interval = [&](int32_t b, int32_t e) { sweep_node.push_back(path_no); sweep_node.push_back(b); sweep_node.push_back(e); sweep_node.push_back(0); };
+      interval(-1000, 2000);  // the events (-1000, 1), (2000, -3000) of graph.cc:3198-3199
+      int32_t pp = 0;
+      for (int32_t e : path) {
+        if (e >= 0) { const int32_t cl = c->g.len(e); if (cl > 0) interval(pp, pp + cl); pp += cl; }  // graph.cc:3202-3210
+        else pp += -e;
+      }
+    }
+    s.misses += en.misses;  // the reference would run BLASR there (out of scope)
+    for (const PbHit& h : en.hits) {
+      count[h.walk]++;
+      if (cov) sweep_occ.push_back(PbOcc{h.walk, h.begin, path_no, 0});  // its records' intervals (graph.cc:3214-3222)
+    }
+  }
+  const double t_after_host = now_us();
+  if (int e = pacbio_sync_records(c, s, st)) return e;
   size_t bytes = align16(std::max<size_t>(1, count.size()) * sizeof(int32_t));  // whole 16-byte units: the copy kernel moves int4s
   void* host = nullptr;
   int slot = stage_acquire(c, s.stage, bytes, &host);

@@ -1,4 +1,4 @@
-// paired_batch.hip.h -- gaml_hip_calc_prob_batch over paired sets: per-set tables from patches / whole, one pass over the records
+// paired_batch.hip.h -- gaml_hip_calc_prob_batch over paired and PacBio sets: per-set tables from patches / whole, one pass over the records
 // (one translation unit with gaml_hip.hip, which includes this file at the place its contents used to stand)
 //
 //   batch_fast_capable    may this context's batches take the one-pass routes at all
@@ -11,13 +11,17 @@
 // ---------------------------------------------------------------------------------------------------------
 // gaml_hip_calc_prob_batch, fast path: up to kMaxSets path sets in ONE pass over the records of every paired set
 // (paired_score_multi_kernel). The host plans the sets one after the other straight into consecutive regions of one
-// arena slot; then one launch per read set, one wait. Contexts with other kinds of read sets or without a memo take the
+// arena slot; then one launch per read set, one wait. Contexts with single-end sets or without a memo take the
 // sequential path of gaml_hip_calc_prob_batch (same results). A set with a coverage penalty goes along: its path sets mark into bitmaps of their
 // own, one sweep dispatch per launch (launch_paired_multi); the wait is then a real stream wait, one per chunk.
+// PacBio sets without a coverage penalty go along as well, beside the paired sets or on their own: one dispatch of
+// pacbio_score_multi_kernel per set and chunk, enqueued before the paired sets are planned (pacbio_batch.hip.h); the wait is
+// a stream wait then too. A PacBio set with a penalty keeps the whole context on the sequential path.
 // ---------------------------------------------------------------------------------------------------------
 static bool batch_fast_capable(const gaml_hip_ctx* c) {
   if (c->handles.empty() || KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_SEQUENTIAL) return false;  // force the sequential path (A/B, tools/)
-  for (auto& h : c->handles) if (h.kind != 1) return false;
+  for (auto& h : c->handles) if (h.kind == 0) return false;
+  for (auto& pb : c->pacbios) if (pb->cfg.penalty_constant > 0) return false;
   for (auto& ps : c->paireds) if (!paired_multi_capable(c, *ps)) return false;
   return true;
 }
@@ -53,15 +57,17 @@ static void multi_drain(gaml_hip_ctx* c) {
   if (!spun) (void)collect_events(c);
 }
 
-// after multi_wait: out[(k * read sets + i) * 4 ..] = {sum, floored, bad bases, reads} of set k, added up in the finisher
-// kernel's order from the set's stripe of pinned partials. record_bad: the penalised sets' counters (handed over behind
+// after multi_wait: out[(k * read sets + slot) * 4 ..] = {sum, floored, bad bases, reads} of set k, added up in the finisher
+// kernel's order from the set's stripe of pinned partials; slot: where combine() expects the read set (scoring_order). The
+// slots of PacBio sets are pacbio_chunk_collect's. record_bad: the penalised sets' counters (handed over behind
 // the partials, store_bad_multi_kernel) and the batch's bookkeeping of them; a pass without penalised sets leaves both alone.
 static void multi_collect(gaml_hip_ctx* c, int n, double* partials_out, bool record_bad) {
-  const size_t nps = c->paireds.size();
+  const size_t nps = c->paireds.size(), ns = c->handles.size();
+  const std::vector<int> slot = slots_of_kind(c, 1);
   for (int k = 0; k < n; k++)
     for (size_t i = 0; i < nps; i++) {
       PairedSet& ps = *c->paireds[i];
-      double* out = partials_out + ((size_t)k * nps + i) * 4;
+      double* out = partials_out + ((size_t)k * ns + (size_t)slot[i]) * 4;
       out[0] = out[1] = out[2] = 0;
       if (ps.last_blocks[k] > 0)
         finisher_order_sum((const double*)ps.h_part_sum.p + (size_t)k * ps.host_part_stride, (const int*)ps.h_part_zero.p + (size_t)k * ps.host_part_stride,
@@ -162,6 +168,8 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     }
     return 0;
   };
+  PbChunk pb(c);
+  if (int e = pacbio_chunk_launch(c, pb, n, paths, offs, set_offs)) return e;
   for (int k = 0; k < n; k++) {
     int64_t pending = 0;
     if (int e = eval_begin(c, paths, offs + set_offs[k], set_offs[k + 1] - set_offs[k], &pending)) return e;
@@ -203,7 +211,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     c->pending_open = false;
     if (pass.due(k)) { if (int e = launch_sets(pass.launched, k + 1)) return e; pass.launched = k + 1; }
   }
-  if (getenv("GAML_HIP_TRACE_HOST")) {
+  if (nps > 0 && getenv("GAML_HIP_TRACE_HOST")) {
     fprintf(stderr, "batch of %d sets, patch entries per set (mate 1 + mate 2):", n);
     for (int k = 0; k < n; k++) fprintf(stderr, " %d+%d", per[0].patch_off[2 * k + 1] - per[0].patch_off[2 * k], per[0].patch_off[2 * k + 2] - per[0].patch_off[2 * k + 1]);
     fprintf(stderr, "\n");
@@ -219,7 +227,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
   _mm_sfence();
   for (size_t i = 0; i < nps; i++) c->paireds[i]->batches_patched++;
   multi_collect(c, n, partials_out, true);
-  return 0;
+  return pacbio_chunk_collect(c, pb, n, partials_out);
 }
 
 // A chunk with whole tables per set, packed by the host into the regions. Returns 1 when a set's tables did not fit the
@@ -257,6 +265,8 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
     }
     return 0;
   };
+  PbChunk pb(c);
+  if (int e = pacbio_chunk_launch(c, pb, n, paths, offs, set_offs)) return e;
   for (int k = 0; k < n; k++) {
     int64_t pending = 0;
     if (int e = eval_begin(c, paths, offs + set_offs[k], set_offs[k + 1] - set_offs[k], &pending)) return e;
@@ -280,6 +290,6 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
   if (int e = multi_wait(c)) return e;
   for (size_t i = 0; i < nps; i++) c->paireds[i]->batches_full++;
   multi_collect(c, n, partials_out, true);
-  return 0;
+  return pacbio_chunk_collect(c, pb, n, partials_out);
 }
 

@@ -298,6 +298,11 @@ int gaml_hip_calc_partials_async(gaml_hip_ctx* ctx, const int32_t* paths, const 
  * library's stream, the host prepares set i+1 while the device scores set i, and there is ONE
  * synchronisation and ONE device->host copy for the whole batch.  Results (and the window cache
  * afterwards) are those of n_sets gaml_hip_calc_prob calls in the same order.
+ * A context of paired sets and / or PacBio sets without coverage penalty (BASELINE config 4: paired + PacBio) scores up
+ * to 8 path sets per pass over the records instead: per chunk one launch per paired set over its records and one per
+ * PacBio set over its cached alignments (occurrence counts of all sets of the chunk side by side per sub-walk), one wait.
+ * Same values bit for bit, same gaml_hip_read_probs / gaml_hip_bad_bases / gaml_hip_pacbio_stats afterwards. A single-end
+ * set or a PacBio set with a coverage penalty keeps the whole context on the path described above.
  *   paths / path_offs : all paths of all sets, concatenated (path k = paths[path_offs[k] .. path_offs[k+1]))
  *   set_offs[n_sets+1]: set i = paths set_offs[i] .. set_offs[i+1]-1
  *   probs_out[n_sets]; zeros_out[n_sets * 2 * num_readsets] and total_lens_out[n_sets] may be NULL.
@@ -403,6 +408,11 @@ int gaml_hip_pair_classes(gaml_hip_ctx* ctx, int readset, int64_t* out4);
  * and therefore never reached the delta lists (since creation), pairs of the compact class whose pair term came with
  * the tables (both records in one window, or a mate without alignment)} */
 int gaml_hip_table_stats(gaml_hip_ctx* ctx, int readset, int64_t* out10);
+/* record cache of a PacBio set: {cached sub-walks, cached records (this shard's reads), sub-walk lookups of the evaluations
+ * so far that found nothing cached (cumulative; the reference would run BLASR there), gaml_hip_calc_prob_batch chunks the
+ * set scored in one multi-set launch}. Host-only contexts too; GAML_HIP_EINVAL for a handle that is not a PacBio set. A
+ * multi-device context reports its first shard, like gaml_hip_table_stats. */
+int gaml_hip_pacbio_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
 /* host-side phase times of the last blocking paired evaluation, microseconds: [0] pass 1 (planner; includes [2]),
  * [1] thresholds + occurrence tables, [2] alignment of newly registered windows (inside pass 1), [3] per-call tables
  * written, [4] record tables / delta lists brought up to date, [5] kernel launches, [6] bytes of per-call tables
