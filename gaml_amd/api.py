@@ -63,7 +63,7 @@ class Knob(enum.IntEnum):
     each one does (tests/test_abi.py holds the two lists together). Every knob is 0 by default."""
     GRID_CAP_COMPACT = 0
     SCORE_LDS_BYTES = 1
-    FINISH_MODE = 2
+    FINISH_MODE = 2  # retired: setting it has no effect
     TIMELINE = 3
     NO_MEMO = 4
     ALIGNER_ROUTE = 5
@@ -94,11 +94,6 @@ KNOB_COUNT = len(Knob)
 
 
 # the values of the knobs that choose between routes (the enums of the same names in gaml_hip_debug.h); 0 is every one's default
-class FinishMode(enum.IntEnum):
-    LAST_BLOCK = 1
-    KERNEL = 2
-
-
 class AlignerRoute(enum.IntEnum):
     HOST = 1
     HOST_SORT = 2

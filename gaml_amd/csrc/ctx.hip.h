@@ -29,6 +29,8 @@
 #include "aligner_file.hip.h"
 #include "host_model.h"
 #include "kernels.hip.h"
+#include "paired_multi.hip.h"
+#include "set_kernels.hip.h"
 #include "table_build.hip.h"
 #include "delta_dev.hip.h"
 #include "pacbio_dp.hip.h"
@@ -563,7 +565,7 @@ struct gaml_hip_ctx {
   double pending_host_us = 0;
   double prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // phase stamps of the last blocking call (us): see gaml_hip_debug_profile
   bool used_default_stream = false;  // an *_async entry point was handed NULL (the legacy default stream) since the last gaml_hip_sync
-  // sharded evaluations: two status words a scoring launch writes with its partials (ticket finish), so that the exchange needs no
+  // sharded evaluations: two status words the finisher kernel of a scoring launch writes with the partials, so that the exchange needs no
   // dispatch of its own for them (multi.hip: ctx_set_status / ctx_status_done)
   double* status_dst = nullptr; double status_a = 0, status_b = 0; bool status_done = false;
   bool host_results = false;  // blocking call: kernels write their results into pinned host memory, no D2H copy

@@ -1,5 +1,5 @@
 // gaml_hip.hip -- context, device memory, launches and the C ABI of libgaml_hip.so.
-// The kernels are in kernels.hip.h, the host data model in host_model.{h,cc}.
+// The scoring kernels are in kernels.hip.h, paired_multi.hip.h and set_kernels.hip.h, the host data model in host_model.{h,cc}.
 #include "ctx.hip.h"
 
 using namespace gaml;
@@ -607,7 +607,7 @@ static int warm_general_kernels(gaml_hip_ctx* c) {
   a.total_blocks = 1;  // main_blocks = 0: the block takes the wave-per-pair branch, whose item count (n - n_main + dstate[kDsSpill]) is 0
   a.dstate = c->warm_buf.as<int>();
   a.part_sum = c->warm_buf.as<double>() + 8; a.part_zero = c->warm_buf.as<int>() + 32;
-  hipLaunchKernelGGL((paired_score_kernel<false, true>), dim3(1), dim3(kBlock), 0, c->stream, a);
+  hipLaunchKernelGGL((paired_score_kernel<true>), dim3(1), dim3(kBlock), 0, c->stream, a);
   MultiSets ms;
   memset((void*)&ms, 0, sizeof(ms));
   ms.skip_classes = 16;  // (the wave-per-pair blocks are "left out": with no path set in `ms` the block returns at once)

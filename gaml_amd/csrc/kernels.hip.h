@@ -1,4 +1,5 @@
-// kernels.hip.h -- hand-written gfx950 kernels of the GAML likelihood path.
+// kernels.hip.h -- hand-written gfx950 kernels of the GAML likelihood path: the shared types and helpers and the single-set
+// paired scorer (the multi-set paired scorer: paired_multi.hip.h; sweeps, single-end and PacBio scorers: set_kernels.hip.h).
 //
 // All three scorers are HBM/L2-streaming reductions (no MFMA: SURVEY.md 8d): one lane owns one
 // read (pair), loads its 16-B alignment records with coalesced dwordx4 loads from the READ-MAJOR
@@ -104,11 +105,6 @@ struct PairedArgs {
   const int2* spill_rng[2];   // long lists: {begin, count} in spill_recs per spill index (a list that changes is written anew behind the others)
   const int4* spill_recs[2];
   const int* spill_slot;      // [n_spill] slot of the pair (scored one WAVE per pair, behind the table pairs with long lists)
-  unsigned* ticket;          // zero before first launch; the last block resets it
-  double* out;               // the read set's 4 partials {sum of logs, floored reads, bad_bases, reads}
-  double n_reads;
-  double* status_out;        // sharded evaluations (stream-ordered, ticket finish): two status words written with the partials, or null
-  double status_a, status_b;
 };
 
 struct Cand { int path, pos, edit, orient, rank, k; bool valid; };
@@ -604,6 +600,18 @@ __device__ __forceinline__ unsigned long long kernel_args_address() {
   return 0;
 #endif
 }
+// the general path for pair i in path set `set` (-1: a single call), its result added to the caller's running sums; COV
+// picks the callee (a multi-set launch that marks coverage)
+template <bool COV>
+__device__ __forceinline__ void compact_general_add(int i, int set, double& lsum, int& zeros) {
+  const GenOut o = COV ? compact_general_call_cov(kernel_args_address(), i, set) : compact_general_call(kernel_args_address(), i, set);
+  lsum += o.add; zeros += o.zeros;
+}
+template <bool COV>
+__device__ __forceinline__ void general_pair_add(int i, int dj, int set, int4* lds, double& lsum, int& zeros) {
+  const GenOut o = COV ? general_pair_call_cov(kernel_args_address(), i, dj, set, lds) : general_pair_call(kernel_args_address(), i, dj, set, lds);
+  lsum += o.add; zeros += o.zeros;
+}
 
 // one scored class-0 pair: per-read probability out, floor / log into the running sums
 __device__ __forceinline__ void compact_finish(const PairedArgs& a, int i, const Compact1& c, const CompactPrep& q, double2 m,
@@ -694,9 +702,9 @@ __device__ __forceinline__ void paired_compact_body(const PairedArgs& a, const S
     const double2 m0 = q0.memo_idx >= 0 ? a.memo[q0.memo_idx] : make_double2(0.0, 0.0);
     const double2 m1 = q1.memo_idx >= 0 ? a.memo[q1.memo_idx] : make_double2(0.0, 0.0);
     if (!d0 && !q0.skip) compact_finish(a, i0, c0, q0, m0, lsum, zeros);
-    else if (GEN && q0.skip) { const GenOut o = compact_general_call(kernel_args_address(), i0, -1); lsum += o.add; zeros += o.zeros; }
+    else if (GEN && q0.skip) compact_general_add<false>(i0, -1, lsum, zeros);
     if (two && !d1 && !q1.skip) compact_finish(a, i1, c1, q1, m1, lsum, zeros);
-    else if (GEN && two && q1.skip) { const GenOut o = compact_general_call(kernel_args_address(), i1, -1); lsum += o.add; zeros += o.zeros; }
+    else if (GEN && two && q1.skip) compact_general_add<false>(i1, -1, lsum, zeros);
     if (!more) break;
     c0 = n0v; c1 = n1v;
     i0 = j0;
@@ -715,20 +723,17 @@ constexpr int kPairZero = -1, kPairOther = -(1 << 20);
 // The coverage events of a scoring class-0 pair (use_all_to_cov, graph.cc:1883-1888) from the 32-bit halves of its records
 // and occurrence entries: both ends of the pair in the region of its path, slot_base[path slot] + shift + position in the
 // window -- the bits compact_cover sets for the same pair. The caller has compared the pair's term with the threshold.
-__device__ __forceinline__ void cover_marks(const PairedArgs& a, uint2 r1, uint2 r2, uint2 o1, uint2 o2) {
-  const int p1 = (int)(__funnelshift_r(r1.x, r1.y, 24) & 0xfffffffu), p2 = (int)(__funnelshift_r(r2.x, r2.y, 24) & 0xfffffffu);
-  const int x = p1 + (int)o1.x, y = p2 + (int)o2.x;
-  const int base = a.path_base[(o1.y >> 16) & 0x7fffu];
-  mark_bit(a.cov_bits, base + max(x, y));
-  mark_bit(a.cov_bits, base + min(x, y));
-}
-// the same into the bitmap of one path set of a multi-set launch (SetDev::cov_bits / slot_base)
+// `bits` / `slot_base`: the bitmap and table of one path set of a multi-set launch (SetDev::cov_bits / slot_base) ...
 __device__ __forceinline__ void cover_marks_set(uint32_t* bits, const int* slot_base, uint2 r1, uint2 r2, uint2 o1, uint2 o2) {
   const int p1 = (int)(__funnelshift_r(r1.x, r1.y, 24) & 0xfffffffu), p2 = (int)(__funnelshift_r(r2.x, r2.y, 24) & 0xfffffffu);
   const int x = p1 + (int)o1.x, y = p2 + (int)o2.x;
   const int base = slot_base[(o1.y >> 16) & 0x7fffu];
   mark_bit(bits, base + max(x, y));
   mark_bit(bits, base + min(x, y));
+}
+// ... or a single call's
+__device__ __forceinline__ void cover_marks(const PairedArgs& a, uint2 r1, uint2 r2, uint2 o1, uint2 o2) {
+  cover_marks_set(a.cov_bits, a.path_base, r1, r2, o1, o2);
 }
 // compact_prep without branches, on the 32-bit halves of the 8-byte record / occurrence words (the scoring kernel
 // is issue-bound at cfg3: the branchy 64-bit form was 156 instructions per pair, a third of a wave's lifetime)
@@ -845,7 +850,7 @@ __device__ __forceinline__ void paired_compact4_body(const PairedArgs& a, const 
     if (GEN && !GAML_GEN_OFF(8) && __any(skip_bits != 0)) {  // pairs on a window that occurs several times: here, after the round's other pairs
 #pragma unroll 1
       for (int k = 0; k < 4; k++)
-        if ((skip_bits >> k) & 1u) { const GenOut o = compact_general_call(kernel_args_address(), (int)(base + k * stride), -1); lsum += o.add; zeros += o.zeros; }
+        if ((skip_bits >> k) & 1u) compact_general_add<false>((int)(base + k * stride), -1, lsum, zeros);
     }
   }
 #undef GAML_STAMP
@@ -878,9 +883,6 @@ __device__ __forceinline__ void paired_compact4_body(const PairedArgs& a, const 
 #ifndef GAML_STATIC_P
 #define GAML_STATIC_P 4
 #endif
-#ifndef GAML_STATIC_PIPE
-#define GAML_STATIC_PIPE 0
-#endif
 // Timing experiments of the development build (results WRONG where a part is switched off; tools/build_variant.sh -DGAML_STATIC_X=..):
 // 1 no occurrence lookups, 2 no stores, 4 no value loads, 8 only the static part of class 0, 16 everything but it. The
 // release library is compiled without any of these arms, whatever is passed on its command line.
@@ -901,9 +903,8 @@ __global__ __launch_bounds__(kBlock) void static_values_kernel(const int* static
   }
 }
 
-// Rounds of P pairs per lane, software-pipelined when a lane takes several: a round's occurrence entries are requested,
-// then the NEXT round's records and values, then the round is finished -- its arithmetic and stores run under the next
-// round's loads.
+// Rounds of P pairs per lane: a round's records and values come in together, then its occurrence entries, then the round is
+// finished; a lane that takes several rounds requests the next round's records and values at the loop's end.
 template <bool GEN, bool TL = false, bool ONE = false, bool COV = false>
 __device__ __forceinline__ void paired_static4_body(const PairedArgs& a, const SlotRange rg, double& lsum, int& zeros) {
   constexpr int P = GAML_STATIC_P;
@@ -941,20 +942,8 @@ __device__ __forceinline__ void paired_static4_body(const PairedArgs& a, const S
       o1[k] = make_uint2(e1->lo, e1->hi); o2[k] = make_uint2(e2->lo, e2->hi);
       if (GAML_TIMING_X(1)) { o1[k] = make_uint2(r1[k].x >> 8, 0u); o2[k] = make_uint2(r1[k].x >> 8, 0u); }
     }
-    // the next round's records (wave-uniform branch; a lane without a next round asks for its first slot again)
     const unsigned nbase = base + P * stride;
     const bool more = nbase < n0;
-    uint2 nr1[P], nr2[P];
-    double2 nm[P];
-    unsigned nlc[P];
-    if (GAML_STATIC_PIPE && __any(more)) {
-#pragma unroll
-      for (int k = 0; k < P; k++) {
-        const unsigned ic = nbase + k * stride < n0 ? nbase + k * stride : base;
-        nr1[k] = *(const uint2*)(rec0 + ic * 8u); nr2[k] = *(const uint2*)(rec1 + ic * 8u); nm[k] = *(const double2*)(sval + ic * 16u);
-        nlc[k] = ONE ? 0u : (unsigned)a.len_code[ic];
-      }
-    }
     GAML_STAMP(3, o1[0].x ^ o2[0].x)
     GAML_STAMP(4, 0u)  // (no memo stage here: the values came in with the records)
     // Everything below is straight-line: bit logic on the 32-bit halves, selects instead of branches, every loaded word
@@ -1001,22 +990,17 @@ __device__ __forceinline__ void paired_static4_body(const PairedArgs& a, const S
     if (GEN && !GAML_GEN_OFF(1) && __any(skip_bits != 0)) {  // pairs on a window that occurs several times: here, after the round's other pairs
 #pragma unroll 1
       for (int k = 0; k < P; k++)
-        if ((skip_bits >> k) & 1u) { const GenOut o = compact_general_call(kernel_args_address(), (int)(base + k * stride), -1); lsum += o.add; zeros += o.zeros; }
+        if ((skip_bits >> k) & 1u) compact_general_add<false>((int)(base + k * stride), -1, lsum, zeros);
     }
     GAML_STAMP(5, 0u)
     first_round = false;
     if (!more) break;
     base = nbase;
-    if (GAML_STATIC_PIPE) {
 #pragma unroll
-      for (int k = 0; k < P; k++) { r1[k] = nr1[k]; r2[k] = nr2[k]; m[k] = nm[k]; lc[k] = nlc[k]; }
-    } else {
-#pragma unroll
-      for (int k = 0; k < P; k++) {
-        const unsigned ic = base + k * stride < n0 ? base + k * stride : base;
-        r1[k] = *(const uint2*)(rec0 + ic * 8u); r2[k] = *(const uint2*)(rec1 + ic * 8u); m[k] = GAML_TIMING_X(4) ? make_double2(1e-9 * (double)ic, -20.0) : *(const double2*)(sval + ic * 16u);
-        lc[k] = ONE ? 0u : (unsigned)a.len_code[ic];
-      }
+    for (int k = 0; k < P; k++) {
+      const unsigned ic = base + k * stride < n0 ? base + k * stride : base;
+      r1[k] = *(const uint2*)(rec0 + ic * 8u); r2[k] = *(const uint2*)(rec1 + ic * 8u); m[k] = GAML_TIMING_X(4) ? make_double2(1e-9 * (double)ic, -20.0) : *(const double2*)(sval + ic * 16u);
+      lc[k] = ONE ? 0u : (unsigned)a.len_code[ic];
     }
   }
 #undef GAML_STAMP
@@ -1242,7 +1226,7 @@ __device__ __forceinline__ void paired_regs_body(const PairedArgs& a, int lb, in
         const int L1 = l12 & 0xffff, L2 = l12 >> 16;
         int4 priv[K == 2 ? 2 * kGenCands : 1];
         if (K == 2 && general_pair_staged<K>(a, r1, r2, L1, L2, acc, slot ? slot : priv)) finish_read(a, i, acc, L1, L2, lsum, zeros);
-        else { const GenOut o = general_pair_call(kernel_args_address(), i, -1, -1, slot); lsum += o.add; zeros += o.zeros; }
+        else general_pair_add<false>(i, -1, -1, slot, lsum, zeros);
       }
 #ifdef GAML_GEN_STAMPS  // (the call as the caller sees it, per LANE that makes it; and how long after the class body's entry it begins)
       if (general) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long tc1_ = wall_clock64(); atomicAdd(&g_gen_stamp[5], tc1_ - tc0_); atomicAdd(&g_gen_stamp[6], 1ull); atomicAdd(&g_gen_stamp[21], tc0_ - tb_); }
@@ -1288,7 +1272,7 @@ __device__ __forceinline__ void paired_delta_body(const PairedArgs& a, int db, i
     if (GEN) {
       if (!GAML_GEN_OFF(4) && __any(general)) {
         int4* const slot = gen_wave_slot(wave_lds, general);
-        if (general) { const GenOut o = general_pair_call(kernel_args_address(), i, dj, -1, slot); lsum += o.add; zeros += o.zeros; }
+        if (general) general_pair_add<false>(i, dj, -1, slot, lsum, zeros);
       }
     } else if (general) {  // cannot happen (a launch without notes has no such window): the partial is poisoned, combine() reports it
       lsum += __builtin_nan("");
@@ -1296,42 +1280,8 @@ __device__ __forceinline__ void paired_delta_body(const PairedArgs& a, int db, i
   }
 }
 
-// delta store maintenance: one thread per patched pair writes its slot, spill index and padded records
-struct DeltaPatch { int dj, slot, spill, pad; int4 rec[2][4]; };
-// the same with room for two records per mate -- the usual delta pair: a node and its twin, a node and a junction -- 80 bytes
-// instead of 144 for the host to write and the device to fetch over PCIe (a patch of a few thousand pairs is what a call costs
-// that activates a window aligned earlier)
-struct DeltaPatch2 { int dj, slot, spill, pad; int4 rec[2][2]; };
-// the class tables' "this pair lives on the delta lists now" marks (one per new delta pair); kDirty8 / kDirtyWid
-__device__ __forceinline__ void mark_dirty_slot(int s, unsigned long long* rec8_0, int n0, int4* inl_0, int n01, int n_main, int4* first_0) {
-  if (s < n0) rec8_0[s] = ~0ull - 1;
-  else {
-    if (s < n01) inl_0[(size_t)2 * (s - n0)].x = -2;
-    else if (s < n_main) inl_0[(size_t)2 * (n01 - n0) + (size_t)4 * (s - n01)].x = -2;
-    first_0[s - n0].x = -2;
-  }
-}
-// `patch` is read where the host wrote it (mapped pinned memory): no copy kernel in front; delta pairs numbered
-// mark_from and up are new with this patch and get their marks here (mark_from < 0: none) -- one dispatch where there
-// were three: copy, patch, marks
-template <class Patch, int K>
-__global__ __launch_bounds__(kBlock) void apply_delta_patch_kernel(const Patch* patch, int n, int* slots, int* spill, int4* rec0, int4* rec1, int mark_from,
-                                                                   unsigned long long* rec8_0, int n0, int4* inl_0, int n01, int n_main, int4* first_0) {
-  for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) {
-    const Patch p = patch[t];
-    slots[p.dj] = p.slot;
-    spill[p.dj] = p.spill;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {  // (the store always holds four records per mate: the short form's missing ones are "none")
-      rec0[4 * (size_t)p.dj + k] = k < K ? p.rec[0][k < K ? k : 0] : make_int4(-1, 0, 0, 0);
-      rec1[4 * (size_t)p.dj + k] = k < K ? p.rec[1][k < K ? k : 0] : make_int4(-1, 0, 0, 0);
-    }
-    if (mark_from >= 0 && p.dj >= mark_from) mark_dirty_slot(p.slot, rec8_0, n0, inl_0, n01, n_main, first_0);
-  }
-}
-
 // TL: the in-kernel timeline of tools/kernel_timeline.py (a separate instantiation: the product kernels carry none of it)
-template <bool TICKET, bool GEN, bool TL, bool COV = false>
+template <bool GEN, bool TL, bool COV = false>
 __device__ __forceinline__ void paired_main_body(const PairedArgs& a, int lb, double* sh_s, int* sh_z, int4* gen_lds) {
   // `a`: the argument block as the kernel received it; only its leading words (grid layout, partial slots) are read
   // here -- every class takes a fresh view of its own (GAML_FRESH_ARGS)
@@ -1382,17 +1332,13 @@ __device__ __forceinline__ void paired_main_body(const PairedArgs& a, int lb, do
   }
   block_reduce(lsum, zeros, sh_s, sh_z);
   if (TL && (threadIdx.x & 63) == 0) tl[6] = wall_clock64();
-  if (TICKET) {
-    GAML_FRESH_ARGS(c, a)
-    grid_finish(lsum, zeros, lb, c.total_blocks, c.part_sum, c.part_zero, c.ticket, c.out,
-                c.cov_bits ? -1.0 : 0.0, c.n_reads, sh_s, sh_z, c.status_out, c.status_a, c.status_b);
-  } else if (threadIdx.x == 0) {
+  if (threadIdx.x == 0) {
     a.part_sum[lb] = lsum;
     a.part_zero[lb] = zeros;
   }
 }
 
-// experiment: separate one-block finisher (sums n_partials partials in index order)
+// the one-block finisher of a stream-ordered paired call: sums n_partials partials in index order (a blocking call's are added by the host)
 __global__ __launch_bounds__(kBlock) void finish_partials_kernel(const double* part_sum, const int* part_zero, int n_partials,
                                                                  double* out, double bad_bases, double n_reads,
                                                                  double* status_out = nullptr, double status_a = 0.0, double status_b = 0.0) {
@@ -1411,7 +1357,7 @@ __global__ __launch_bounds__(kBlock) void finish_partials_kernel(const double* p
 // The wave gathers every (record, occurrence) candidate of both mates into LDS,
 // settles the overwrite rule in parallel and spreads the x * y pair terms over its lanes;
 // deterministic lane-strided + butterfly summation. It reads nothing the main kernel writes, so
-// both run concurrently (two streams); they share one ticket, and whichever block finishes last
+// both run in one launch; every block stores its partial, and the host or the finisher kernel
 // folds all per-block partials in index order.
 constexpr int kOvfMaxBlocks = 1024;
 
@@ -1493,7 +1439,6 @@ __device__ __forceinline__ double wave_score_pair(const PairedArgs& a, const Src
   return acc;
 }
 
-template <bool TICKET>
 __device__ __forceinline__ void paired_overflow_body(const PairedArgs& a, int ovf_block, int ovf_blocks, double* sh_s, int* sh_z,
                                                      int4 (*cand)[2][kOvfCap]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1525,10 +1470,7 @@ __device__ __forceinline__ void paired_overflow_body(const PairedArgs& a, int ov
     }
   }
   block_reduce(lsum, zeros, sh_s, sh_z);
-  if (TICKET) {
-    grid_finish(lsum, zeros, a.main_blocks + ovf_block, a.total_blocks, a.part_sum, a.part_zero, a.ticket, a.out,
-                a.cov_bits ? -1.0 : 0.0, a.n_reads, sh_s, sh_z, a.status_out, a.status_a, a.status_b);
-  } else if (threadIdx.x == 0) {
+  if (threadIdx.x == 0) {
     a.part_sum[a.main_blocks + ovf_block] = lsum;
     a.part_zero[a.main_blocks + ovf_block] = zeros;
   }
@@ -1545,7 +1487,7 @@ __device__ __forceinline__ void paired_overflow_body(const PairedArgs& a, int ov
 #endif
 // COV: a set with a coverage penalty whose class 0 takes the memo / streamed-value bodies and marks from there (launch_paired
 // picks it for penalised sets without repeated windows; every other combination runs the instantiations without it).
-template <bool TICKET, bool GEN = false, bool TL = false, bool COV = false>
+template <bool GEN = false, bool TL = false, bool COV = false>
 __global__ __launch_bounds__(kBlock, GEN ? GAML_GEN_WAVES : 5) void paired_score_kernel(PairedArgs a) {
   __shared__ double sh_s[kBlock / 64];
   __shared__ int sh_z[kBlock / 64];
@@ -1566,927 +1508,19 @@ __global__ __launch_bounds__(kBlock, GEN ? GAML_GEN_WAVES : 5) void paired_score
     if (!GAML_TIMING_X(16))
     paired_static4_body<GEN, false, true, COV>(a, SlotRange{0, a.n0a, lb, a.blocks0a}, lsum, zeros);
     block_reduce(lsum, zeros, sh_s, sh_z);
-    if (TICKET) grid_finish(lsum, zeros, lb, a.total_blocks, a.part_sum, a.part_zero, a.ticket, a.out, COV ? -1.0 : 0.0, a.n_reads, sh_s, sh_z, a.status_out, a.status_a, a.status_b);
-    else if (threadIdx.x == 0) { a.part_sum[lb] = lsum; a.part_zero[lb] = zeros; }
+    if (threadIdx.x == 0) { a.part_sum[lb] = lsum; a.part_zero[lb] = zeros; }
     return;
   }
-  if (lb < a.main_blocks) paired_main_body<TICKET, GEN, TL, COV>(a, lb, sh_s, sh_z, &cand[0][0][0]);
+  if (lb < a.main_blocks) paired_main_body<GEN, TL, COV>(a, lb, sh_s, sh_z, &cand[0][0][0]);
   else if (GAML_GEN_OFF(16)) { if (threadIdx.x == 0) { a.part_sum[lb] = 0.0; a.part_zero[lb] = 0; } }
   else {
     GAML_FRESH_ARGS(c, a)
-    paired_overflow_body<TICKET>(c, lb - c.main_blocks, c.total_blocks - c.main_blocks, sh_s, sh_z, cand);
+    paired_overflow_body(c, lb - c.main_blocks, c.total_blocks - c.main_blocks, sh_s, sh_z, cand);
   }
 #else
-  if (lb < a.main_blocks) paired_main_body<TICKET, GEN, TL, COV>(a, lb, sh_s, sh_z, &cand[0][0][0]);
-  else paired_overflow_body<TICKET>(a, lb - a.main_blocks, a.total_blocks - a.main_blocks, sh_s, sh_z, cand);
+  if (lb < a.main_blocks) paired_main_body<GEN, TL, COV>(a, lb, sh_s, sh_z, &cand[0][0][0]);
+  else paired_overflow_body(a, lb - a.main_blocks, a.total_blocks - a.main_blocks, sh_s, sh_z, cand);
 #endif
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Several path sets in ONE pass over the records (gaml_hip_calc_prob_batch; the move generators compare a handful of
-// near-identical candidate assemblies: moves.cc:107-113 LocalChange2, 694-800 FixGapLength, 1156-1305 FixRepForNode2).
-// A path set only changes WHERE windows sit (its occurrence tables, 12 B per window) and 2T; the records, the
-// memo of pair terms and the grid are the same for all of them. So: the compact class (90 % of the pairs) loads
-// its 8-byte records once and resolves them against every set's tables (S x 95 KB at cfg3: L2 resident) in an inner
-// loop; the other classes (10 % of the pairs, a few records each, L2 hits after the first set) simply run their body
-// once per set. Every (block, set) writes its own partial: same lane -> pair mapping and reduction order as the
-// single-set kernel, so a batch gives bit for bit what the sets give one by one.
-// ---------------------------------------------------------------------------------------------------------
-constexpr int kMaxSets = 8;
-struct SetDev {  // what differs between the path sets of one batch
-  const Occ12* occ12[2];
-  const int* multi_off[2];
-  const int4* multi[2];
-  const double* tfloor_c;          // [code] for this set's 2T
-  double tfloor0;                  // = tfloor_c[0], by value
-  double two_T, log_two_T;
-  double* part_sum;                // this set's per-block partials
-  int* part_zero;
-  // a set with a coverage penalty: its own bitmap (a region of the launch's buffer at a 32-bit-aligned offset) and its own
-  // slot_base table -- PairedArgs::cov_bits / path_base of a single call; null for a set without penalty
-  uint32_t* cov_bits;
-  const int* slot_base;
-};
-// chg[mt][w]: bit s set = window w's table entry in set s of this launch may differ from set 0's (s >= 1; a batch whose
-// sets' tables were built from patches knows, batch_tables_kernel). A pair none of whose records touch such a window
-// resolves to the same candidates in set s as in set 0: its set-0 result is finished again under set s's 2T and
-// thresholds, no table is read. The bits are cumulative (bit s implies bit s + 1: a set's tables are its
-// predecessor's plus a patch). Null: unknown, every set resolves every pair. Used by the classes with several records
-// per pair and the delta / wave-per-pair blocks; the compact class resolves every set (see its body).
-struct MultiSets { int n; int skip_classes; const unsigned char* chg[2]; SetDev set[kMaxSets]; };
-
-constexpr int kTfCodes = 16;  // length codes whose per-set thresholds a multi-set block keeps in LDS
-// COV: the launch marks coverage -- the set's bitmap and slot_base table travel too (pair_term, compact_cover and the general
-// paths then mark into this set's bitmap); without it the view is what it always was
-template <bool COV = false>
-__device__ __forceinline__ PairedArgs with_set(const PairedArgs& a, const SetDev& sd, const double* tfloor_lds = nullptr) {
-  PairedArgs b = a;
-  if (COV) { b.cov_bits = sd.cov_bits; b.path_base = sd.slot_base; }
-#pragma unroll
-  for (int mt = 0; mt < 2; mt++) { b.m[mt].occ12 = sd.occ12[mt]; b.occ12[mt] = sd.occ12[mt]; b.m[mt].multi_off = sd.multi_off[mt]; b.m[mt].multi = sd.multi[mt]; }
-  b.tfloor_c = tfloor_lds ? tfloor_lds : sd.tfloor_c; b.tfloor0 = sd.tfloor0; b.two_T = sd.two_T; b.log_two_T = sd.log_two_T;
-  b.part_sum = sd.part_sum; b.part_zero = sd.part_zero;
-  return b;
-}
-
-// the kernel's argument block, read where it is needed (a callee's view of it); a multi-set launch's: {PairedArgs, MultiSets}
-struct MultiKernArgs { PairedArgs a; MultiSets ms; };
-#if defined(__HIP_DEVICE_COMPILE__)
-#define GAML_CALLEE_ARGS(name, set, COV)                                                                                             \
-  const unsigned long long name##_u = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(kernargs >> 32)) << 32) |  \
-                                      (unsigned)__builtin_amdgcn_readfirstlane((int)kernargs); /* (uniform: scalar loads) */         \
-  const __attribute__((address_space(4))) MultiKernArgs* name##_p = (const __attribute__((address_space(4))) MultiKernArgs*)name##_u; \
-  const PairedArgs name##_0 = name##_p->a;                                                                                           \
-  const PairedArgs name = (set) >= 0 ? with_set<COV>(name##_0, name##_p->ms.set[set]) : name##_0;
-#else
-#define GAML_CALLEE_ARGS(name, set, COV) const PairedArgs& name = *(const PairedArgs*)nullptr;
-#endif
-template <bool COV>
-__device__ __forceinline__ GenOut compact_general_impl(unsigned long long kernargs, int i, int set) {
-  GAML_CALLEE_ARGS(a, set, COV)
-  GenOut o{0.0, 0};
-  compact_general(a, i, o.add, o.zeros);
-  return o;
-}
-__device__ __noinline__ GenOut compact_general_call(unsigned long long kernargs, int i, int set) { return compact_general_impl<false>(kernargs, i, set); }
-__device__ __noinline__ GenOut compact_general_call_cov(unsigned long long kernargs, int i, int set) { return compact_general_impl<true>(kernargs, i, set); }
-template <bool COV>
-__device__ __forceinline__ GenOut general_pair_impl(unsigned long long kernargs, int i, int dj, int set, int4* lds) {
-  GAML_CALLEE_ARGS(a, set, COV)
-  GenOut o{0.0, 0};
-  int4 priv[2 * kGenCands];
-  int4* const cand = lds ? lds : priv;
-  const int4 none = make_int4(-1, 0, 0, 0);
-  int4 r1[4], r2[4];
-  double acc;
-  if (dj < 0) {  // a table pair of class 1 / 2: its inline copies
-    const bool four = i >= a.n01;
-    const size_t at = four ? (size_t)2 * (a.n01 - a.n0) + (size_t)4 * (i - a.n01) : (size_t)2 * (i - a.n0);
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const bool has = four || k < 2; r1[k] = has ? a.inl[0][at + (has ? k : 0)] : none; r2[k] = has ? a.inl[1][at + (has ? k : 0)] : none; }
-    const uint32_t l12 = a.len12[i - a.n0];
-    const int L1 = l12 & 0xffff, L2 = l12 >> 16;
-    if (!general_pair_staged<4>(a, r1, r2, L1, L2, acc, cand)) acc = paired_general(a, a.m[0].first[i - a.n0], a.m[1].first[i - a.n0], L1, L2);
-    finish_read(a, i, acc, L1, L2, o.add, o.zeros);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; k++) { r1[k] = a.dirty_recs[0][4 * (size_t)dj + k]; r2[k] = a.dirty_recs[1][4 * (size_t)dj + k]; }
-    const uint32_t l12 = (uint32_t)r1[0].w;
-    const int L1 = l12 & 0xffff, L2 = l12 >> 16;
-    const int c0 = r2[0].w & 0xff, c1 = (r2[0].w >> 8) & 0xff;
-    if (!general_pair_staged<4>(a, r1, r2, L1, L2, acc, cand))
-      acc = paired_general_src_masks(a, ListSrc{a.dirty_recs[0] + 4 * (size_t)dj, c0}, ListSrc{a.dirty_recs[1] + 4 * (size_t)dj, c1}, L1, L2);
-    finish_read(a, i, acc, L1, L2, o.add, o.zeros);
-  }
-  return o;
-}
-__device__ __noinline__ GenOut general_pair_call(unsigned long long kernargs, int i, int dj, int set, int4* lds) { return general_pair_impl<false>(kernargs, i, dj, set, lds); }
-__device__ __noinline__ GenOut general_pair_call_cov(unsigned long long kernargs, int i, int dj, int set, int4* lds) { return general_pair_impl<true>(kernargs, i, dj, set, lds); }
-
-// paired_compact4_body with the path sets in the inner loop. acc_s / acc_z: one running sum per (set, thread) in LDS
-// (a lane may take several rounds of four pairs; registers cannot be indexed by the set number).
-// COV: a launch of penalised sets -- a pair whose term clears the threshold marks both its ends in THIS set's bitmap, where
-// paired_compact4_body<.., COV> marks them in the call's.
-template <bool GEN, bool ONE, bool COV = false>
-__device__ __forceinline__ void paired_compact4_multi_body(const PairedArgs& a, const MultiSets& ms, const SlotRange rg, double* acc_s, int* acc_z, const double* tf) {
-  const unsigned stride = (unsigned)rg.blocks * kBlock, n0 = (unsigned)rg.hi;  // (n0: end of this part's slots)
-  const char* const rec0 = (const char*)a.rec8[0];
-  const char* const rec1 = (const char*)a.rec8[1];
-  const char* const memo = (const char*)a.memo;
-  char* const probs = (char*)a.probs;
-  const uint32_t l12_one = ONE ? a.len_combo[0] : 0u;
-  const double logfloor_one = ONE ? a.logfloor_c[0] : 0.0;
-  const double covthr_one = COV && ONE ? a.covthr0 : 0.0;
-  for (unsigned base = (unsigned)rg.lo + (unsigned)rg.lb * kBlock + threadIdx.x; base < n0; base += 4 * stride) {
-    uint2 r1[4], r2[4];
-    unsigned lc[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {  // the records: ONCE for all sets
-      const unsigned ic = base + k * stride < n0 ? base + k * stride : base;
-      r1[k] = *(const uint2*)(rec0 + ic * 8u); r2[k] = *(const uint2*)(rec1 + ic * 8u); lc[k] = ONE ? 0u : (unsigned)a.len_code[ic];
-    }
-    // (Every set resolves every pair here. Finishing a pair from its set-0 result where no window of it changed -- as the
-    // other classes do -- does not pay in this class: the launch lasts as long as its slowest wavefront, and some
-    // wavefront always holds a pair on a changed window; the bookkeeping only costs registers. Measured: 26.1 us for
-    // four sets this way, 28.7 us with the capture, tools/batch_ablate.py.)
-#pragma unroll 1
-    for (int s = 0; s < ms.n; s++) {
-      const SetDev& sd = ms.set[s];
-      const char* const occ0 = (const char*)sd.occ12[0];
-      const char* const occ1 = (const char*)sd.occ12[1];
-      const double* const tfs = tf ? tf + s * kTfCodes : sd.tfloor_c;  // this set's thresholds per length code (LDS copy when it fits)
-      const double log2T = sd.log_two_T, tfloor_one = ONE ? tfs[0] : 0.0;
-      const bool last_set = s == ms.n - 1;  // per-read probabilities: those of the last set, as after a sequence of calls
-      uint2 o1[4], o2[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const Occ12* e1 = (const Occ12*)(occ0 + (r1[k].y != ~0u ? (r1[k].x & 0xffffffu) : 0u) * 12u);
-        const Occ12* e2 = (const Occ12*)(occ1 + (r2[k].y != ~0u ? (r2[k].x & 0xffffffu) : 0u) * 12u);
-        o1[k] = make_uint2(e1->lo, e1->hi); o2[k] = make_uint2(e2->lo, e2->hi);
-      }
-      int state[4];
-      unsigned skip_bits = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        bool skip;
-        state[k] = compact_state(a, r1[k], r2[k], o1[k], o2[k], lc[k], ONE ? l12_one : a.len_combo[lc[k]], base + k * stride < n0, skip);
-        skip_bits |= (unsigned)skip << k;
-      }
-      double2 m[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) m[k] = *(const double2*)(memo + (unsigned)max(state[k], 0) * 16u);
-      double lsum = 0.0;
-      int zeros = 0;
-      bool other = false;
-      unsigned mark_bits = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        double* const out = (double*)(probs + (base + k * stride) * 8u);
-        if (state[k] >= 0) {
-          if (COV) mark_bits |= (unsigned)(m[k].x > (ONE ? covthr_one : a.covthr_c[lc[k]])) << k;
-          if (last_set) __builtin_nontemporal_store(m[k].x, out);
-          const bool floored = m[k].x < (ONE ? tfloor_one : tfs[lc[k]]);
-          lsum += floored ? (ONE ? logfloor_one : a.logfloor_c[lc[k]]) : m[k].y - log2T;
-          zeros += (int)floored;
-        } else if (state[k] > kPairOther) {
-          if (last_set) __builtin_nontemporal_store(0.0, out);
-          zeros++;
-          lsum += ONE ? logfloor_one : a.logfloor_c[kPairZero - state[k]];
-        } else other |= state[k] == kPairOther && !((skip_bits >> k) & 1u);
-      }
-      if (COV) {  // behind the set's sums and stores, as in the single-set body
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if ((mark_bits >> k) & 1u) cover_marks_set(sd.cov_bits, sd.slot_base, r1[k], r2[k], o1[k], o2[k]);
-      }
-      if (__any(other)) {  // scores, but outside the memo: from the tables (rare)
-        const PairedArgs b = with_set<COV>(a, sd, tf ? tfs : nullptr);
-#pragma unroll 1
-        for (int k = 0; k < 4; k++) {
-          if (state[k] != kPairOther || ((skip_bits >> k) & 1u)) continue;
-          const int i = (int)(base + k * stride);
-          Compact1 d;
-          compact_load(b, i, true, d);
-          d.o1 = d.r1 != kNone8 ? occ8_of(b.occ12[0], (unsigned)(d.r1 & 0xffffff)) : kNone8;
-          d.o2 = d.r2 != kNone8 ? occ8_of(b.occ12[1], (unsigned)(d.r2 & 0xffffff)) : kNone8;
-          const uint32_t l = b.len_combo[d.lc];
-          d.L1 = l & 0xffff; d.L2 = l >> 16;
-          CompactPrep q;
-          compact_prep(b, d, q);
-          compact_finish(b, i, d, q, make_double2(0.0, 0.0), lsum, zeros);
-        }
-      }
-      if (GEN && __any(skip_bits != 0)) {  // as paired_compact4_body
-#pragma unroll 1
-        for (int k = 0; k < 4; k++)
-          if ((skip_bits >> k) & 1u) { const GenOut o = COV ? compact_general_call_cov(kernel_args_address(), (int)(base + k * stride), s) : compact_general_call(kernel_args_address(), (int)(base + k * stride), s); lsum += o.add; zeros += o.zeros; }
-      }
-      acc_s[s * kBlock + threadIdx.x] += lsum;
-      acc_z[s * kBlock + threadIdx.x] += zeros;
-    }
-  }
-}
-
-// paired_static4_body with the path sets in the inner loop: the static pairs' records AND values come in once for all sets
-// (the per-set arithmetic above goes records -> occurrence entries -> memo index -> memo entry, two dependent trips per set;
-// here a set costs one: its occurrence entries). Lanes, pairs, the values added and their order are the single-set
-// kernel's: a batch gives bit for bit what the sets give one by one.
-template <bool GEN, bool ONE, bool COV = false>
-__device__ __forceinline__ void paired_static4_multi_body(const PairedArgs& a, const MultiSets& ms, const SlotRange rg, double* acc_s, int* acc_z, const double* tf) {
-  const unsigned stride = (unsigned)rg.blocks * kBlock, n0 = (unsigned)rg.hi;
-  const char* const rec0 = (const char*)a.rec8[0];
-  const char* const rec1 = (const char*)a.rec8[1];
-  const char* const sval = (const char*)a.static_val;
-  char* const probs = (char*)a.probs;
-  const double logfloor_one = ONE ? a.logfloor_c[0] : 0.0;
-  const double covthr_one = COV && ONE ? a.covthr0 : 0.0;
-  for (unsigned base = (unsigned)rg.lo + (unsigned)rg.lb * kBlock + threadIdx.x; base < n0; base += 4 * stride) {
-    uint2 r1[4], r2[4];
-    double2 m[4];
-    unsigned lc[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {  // records and values: ONCE for all sets
-      const unsigned ic = base + k * stride < n0 ? base + k * stride : base;
-      r1[k] = *(const uint2*)(rec0 + ic * 8u); r2[k] = *(const uint2*)(rec1 + ic * 8u); m[k] = *(const double2*)(sval + ic * 16u);
-      lc[k] = ONE ? 0u : (unsigned)a.len_code[ic];
-    }
-#pragma unroll 1
-    for (int s = 0; s < ms.n; s++) {
-      const SetDev& sd = ms.set[s];
-      const char* const occ0 = (const char*)sd.occ12[0];
-      const char* const occ1 = (const char*)sd.occ12[1];
-      const double* const tfs = tf ? tf + s * kTfCodes : sd.tfloor_c;
-      const double log2T = sd.log_two_T, tfloor_one = ONE ? tfs[0] : 0.0;
-      const bool last_set = s == ms.n - 1;
-      uint2 o1[4], o2[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const unsigned w1 = (r1[k].x & 0xffffffu) & (0u - (unsigned)(r1[k].y != ~0u)), w2 = (r2[k].x & 0xffffffu) & (0u - (unsigned)(r2[k].y != ~0u));
-        const Occ12* e1 = (const Occ12*)(occ0 + w1 * 12u);
-        const Occ12* e2 = (const Occ12*)(occ1 + w2 * 12u);
-        o1[k] = make_uint2(e1->lo, e1->hi); o2[k] = make_uint2(e2->lo, e2->hi);
-      }
-      double lsum = acc_s[s * kBlock + threadIdx.x];  // (the running sum of this lane and set: additions in the single-set kernel's order)
-      int zeros = acc_z[s * kBlock + threadIdx.x];
-      unsigned skip_bits = 0, mark_bits = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {  // as paired_static4_body, statement for statement
-        const bool none1 = r1[k].y == ~0u, none2 = r2[k].y == ~0u;
-        const bool here = (base + k * stride < n0) & !(none1 & (r1[k].x == 0xfffffffeu));
-        const bool w1 = !none1 & (o1[k].y != ~0u), w2 = !none2 & (o2[k].y != ~0u);
-        const bool gen = here & ((w1 & ((int)o1[k].y < 0)) | (w2 & ((int)o2[k].y < 0)));
-        const bool same = (o1[k].x == o2[k].x) & (((o1[k].y ^ o2[k].y) >> 16) == 0);
-        const int p1 = (int)(__funnelshift_r(r1[k].x, r1[k].y, 24) & 0xfffffffu), p2 = (int)(__funnelshift_r(r2[k].x, r2[k].y, 24) & 0xfffffffu);
-        const bool kept = (p1 >= (int)(short)(o1[k].y & 0xffffu)) & (p2 >= (int)(short)(o2[k].y & 0xffffu));
-        const bool both = here & !gen & w1 & w2;
-        const bool scores = both & same & kept;
-        const bool poison = both & !same;
-        const bool counted = here & !gen;
-        skip_bits |= (unsigned)gen << k;
-        const double t = scores ? m[k].x : 0.0;
-        const bool floored = counted & (!scores | (t < (ONE ? tfloor_one : tfs[lc[k]])));
-        const double lf = ONE ? logfloor_one : a.logfloor_c[lc[k]];
-        double add = floored ? lf : m[k].y - log2T;
-        add = counted ? add : 0.0;
-        add = poison ? __builtin_nan("") : add;
-        lsum += add;
-        zeros += (int)floored;
-        if (counted && last_set) __builtin_nontemporal_store(t, (double*)(probs + (base + k * stride) * 8u));
-        if (COV) mark_bits |= (unsigned)(scores & (t > (ONE ? covthr_one : a.covthr_c[lc[k]]))) << k;
-      }
-      if (COV) {  // behind the set's sums and stores, into this set's bitmap
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if ((mark_bits >> k) & 1u) cover_marks_set(sd.cov_bits, sd.slot_base, r1[k], r2[k], o1[k], o2[k]);
-      }
-      if (GEN && __any(skip_bits != 0)) {  // as paired_static4_body
-#pragma unroll 1
-        for (int k = 0; k < 4; k++)
-          if ((skip_bits >> k) & 1u) { const GenOut o = COV ? compact_general_call_cov(kernel_args_address(), (int)(base + k * stride), s) : compact_general_call(kernel_args_address(), (int)(base + k * stride), s); lsum += o.add; zeros += o.zeros; }
-      }
-      acc_s[s * kBlock + threadIdx.x] = lsum;
-      acc_z[s * kBlock + threadIdx.x] = zeros;
-    }
-  }
-}
-
-// Classes 1 and 2 with the path sets in the inner loop (paired_regs_body's pairs, lane -> pair mapping and order of
-// additions): records once, set 0 resolved and captured, later sets finished from the capture unless one of the
-// pair's windows changed.
-template <int K, bool GEN, bool COV = false>
-__device__ __forceinline__ void paired_regs_multi_body(const PairedArgs& a, const MultiSets& ms, int lb, int slot_lo, int slot_hi, int block_lo,
-                                                       int block_hi, double* acc_s, int* acc_z, const double* tf) {
-  for (int i = slot_lo + (lb - block_lo) * kBlock + threadIdx.x; i < slot_hi; i += (block_hi - block_lo) * kBlock) {
-    const uint32_t l12 = a.len12[i - a.n0];
-    const size_t at = K == 2 ? (size_t)2 * (i - a.n0) : (size_t)2 * (a.n01 - a.n0) + (size_t)4 * (i - a.n01);
-    int4 r1[K], r2[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) { r1[k] = a.inl[0][at + k]; r2[k] = a.inl[1][at + k]; }
-    const bool dirty = r1[0].x == kDirtyWid;  // scored from the delta lists
-    unsigned chg = ms.chg[0] ? 0u : 0xffu;
-    if (ms.chg[0] && !dirty) {
-#pragma unroll
-      for (int k = 0; k < K; k++) chg |= (r1[k].x >= 0 ? ms.chg[0][r1[k].x] : 0u) | (r2[k].x >= 0 ? ms.chg[1][r2[k].x] : 0u);
-    }
-    PairVal val{0.0, 0.0, 0, 0};
-    bool general = false;
-#pragma unroll 1
-    for (int s = 0; s < ms.n; s++) {
-      const PairedArgs b = with_set<COV>(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
-      double lsum = acc_s[s * kBlock + threadIdx.x];
-      int zeros = acc_z[s * kBlock + threadIdx.x];
-      if (s == 0 || ((chg >> s) & 1u)) {
-        RegCands<K> x, y;
-        const bool m1 = cands_from_records<K>(b.m[0], r1, x), m2 = cands_from_records<K>(b.m[1], r2, y);
-        general = !dirty && (m1 || m2);  // a window that occurs several times: general_pair_call
-        val.kind = 0;
-        if (!dirty && !general) score_cands_and_finish<K>(b, i, l12, x, y, lsum, zeros, &val);
-      } else {
-        finish_val(b, i, val, s == ms.n - 1, lsum, zeros);
-      }
-      if (GEN && general) { const GenOut o = COV ? general_pair_call_cov(kernel_args_address(), i, -1, s, nullptr) : general_pair_call(kernel_args_address(), i, -1, s, nullptr); lsum += o.add; zeros += o.zeros; }  // (in every set: val holds nothing of such a pair)
-      acc_s[s * kBlock + threadIdx.x] = lsum;
-      acc_z[s * kBlock + threadIdx.x] = zeros;
-    }
-  }
-}
-
-// paired_delta_body with the path sets in the inner loop
-template <bool GEN, bool COV = false>
-__device__ __forceinline__ void paired_delta_multi_body(const PairedArgs& a, const MultiSets& ms, int db, int delta_blocks, double* acc_s, int* acc_z, const double* tf) {
-  for (int dj = db * kBlock + threadIdx.x; dj < a.dstate[kDsDirty]; dj += delta_blocks * kBlock) {
-    const int i = a.dirty_slots[dj];
-    const int sp = a.dirty_spill[dj];
-    const bool mine = sp < 0;  // (sp >= 0, a long list: one WAVE scores it. Such a lane stays in the loop: the note words are
-                               // written by the wave's lane 0 from a ballot over ALL its lanes)
-    int4 r0[4], r1[4];
-    int c0 = 0, c1 = 0;
-    unsigned chg = ms.chg[0] ? 0u : 0xffu;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      r0[k] = a.dirty_recs[0][4 * (size_t)dj + k];
-      r1[k] = a.dirty_recs[1][4 * (size_t)dj + k];
-      c0 += r0[k].x >= 0; c1 += r1[k].x >= 0;
-      if (ms.chg[0]) chg |= (r0[k].x >= 0 ? ms.chg[0][r0[k].x] : 0u) | (r1[k].x >= 0 ? ms.chg[1][r1[k].x] : 0u);
-    }
-    const uint32_t l12 = (uint32_t)r0[0].w;  // the pair's read lengths travel with its first record (paired_upload_delta)
-    PairVal val{0.0, 0.0, 0, 0};
-    bool general = false;  // as resolved last: a set whose tables agree with its predecessor's on this pair's windows inherits it
-#pragma unroll 1
-    for (int s = 0; s < ms.n; s++) {
-      const PairedArgs b = with_set<COV>(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
-      double lsum = acc_s[s * kBlock + threadIdx.x];
-      int zeros = acc_z[s * kBlock + threadIdx.x];
-      if (!mine) {
-      } else if (s == 0 || ((chg >> s) & 1u)) {
-        RegCands<4> x, y;
-        const bool m0 = cands_from_records<4>(b.m[0], r0, x), m1 = cands_from_records<4>(b.m[1], r1, y);
-        general = m0 || m1;  // a window that occurs several times in this path set: general_pair_call (as paired_delta_body)
-        val.kind = 0;
-        if (!general) score_cands_and_finish<4>(b, i, l12, x, y, lsum, zeros, &val);
-        else if (!GEN) lsum += __builtin_nan("");  // cannot happen (a launch without notes has no such window): poisoned, reported by combine()
-      } else {
-        finish_val(b, i, val, s == ms.n - 1, lsum, zeros);
-      }
-      if (GEN && mine && general) { const GenOut o = COV ? general_pair_call_cov(kernel_args_address(), i, dj, s, nullptr) : general_pair_call(kernel_args_address(), i, dj, s, nullptr); lsum += o.add; zeros += o.zeros; }
-      acc_s[s * kBlock + threadIdx.x] = lsum;
-      acc_z[s * kBlock + threadIdx.x] = zeros;
-    }
-  }
-}
-
-// the sets (bits) in which one of a pair's windows changed, over all its records of one mate: lanes stride, wave OR
-template <class Src>
-__device__ __forceinline__ unsigned wave_changed(const Src& src, const unsigned char* chg, int lane) {
-  unsigned m = 0;
-  const int cnt = src.count();
-  for (int k = lane; k < cnt; k += 64) { const int4 r = src.get(k); if (r.x >= 0) m |= chg[r.x]; }
-  for (int off = 32; off > 0; off >>= 1) m |= __shfl_xor(m, off, 64);
-  return m;
-}
-
-// paired_overflow_body with the path sets in the inner loop: wave w keeps its running sums per set in acc (lane 0's)
-template <bool COV = false>
-__device__ __forceinline__ void paired_overflow_multi_body(const PairedArgs& a, const MultiSets& ms, int ovf_block, int ovf_blocks,
-                                                           int4 (*cand)[2][kOvfCap], double* acc_s, int* acc_z, const double* tf) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wave_global = ovf_block * (kBlock / 64) + wave;
-  const int n_waves = ovf_blocks * (kBlock / 64);
-  const int n_table = a.n - a.n_main;
-  const int n_items = n_table + a.dstate[kDsSpill];
-  int4* c1 = cand[wave][0];
-  int4* c2 = cand[wave][1];
-  for (int item = wave_global; item < n_items; item += n_waves) {  // fixed item -> wave assignment
-    int i, L1, L2;
-    TableSrc t1{&a.m[0], make_int4(-1, 0, 0, 0)}, t2{&a.m[1], make_int4(-1, 0, 0, 0)};
-    ListSrc l1{nullptr, 0}, l2{nullptr, 0};
-    const bool table = item < n_table;
-    if (table) {
-      i = a.n_main + item;
-      t1.r0 = a.m[0].first[i - a.n0]; t2.r0 = a.m[1].first[i - a.n0];
-      const uint32_t l12 = a.len12[i - a.n0];
-      if (t1.r0.x == kDirtyWid) continue;  // a class-3 pair that is on the delta list: scored there
-      L1 = l12 & 0xffff; L2 = l12 >> 16;
-    } else {
-      const int sp = item - n_table;
-      i = a.spill_slot[sp];
-      const uint32_t l12 = i < a.n0 ? a.len_combo[a.len_code[i]] : a.len12[i - a.n0];
-      L1 = l12 & 0xffff; L2 = l12 >> 16;
-      const int2 g0 = a.spill_rng[0][sp], g1 = a.spill_rng[1][sp];
-      l1 = ListSrc{a.spill_recs[0] + g0.x, g0.y};
-      l2 = ListSrc{a.spill_recs[1] + g1.x, g1.y};
-    }
-    unsigned chg = 0xffu;
-    if (ms.chg[0]) chg = table ? (wave_changed(t1, ms.chg[0], lane) | wave_changed(t2, ms.chg[1], lane)) : (wave_changed(l1, ms.chg[0], lane) | wave_changed(l2, ms.chg[1], lane));
-    PairVal val{0.0, 0.0, 0, 0};
-    for (int s = 0; s < ms.n; s++) {
-      const PairedArgs b = with_set<COV>(a, ms.set[s], tf ? tf + s * kTfCodes : nullptr);
-      double lsum = 0.0;
-      int zeros = 0;
-      if (s == 0 || ((chg >> s) & 1u)) {  // wave-uniform
-        TableSrc u1{&b.m[0], t1.r0}, u2{&b.m[1], t2.r0};
-        const double acc = table ? wave_score_pair(b, u1, u2, L1, L2, c1, c2, lane) : wave_score_pair(b, l1, l2, L1, L2, c1, c2, lane);
-        if (lane == 0) finish_read(b, i, acc, L1, L2, lsum, zeros, &val);
-      } else if (lane == 0) {
-        finish_val(b, i, val, s == ms.n - 1, lsum, zeros);
-      }
-      if (lane == 0) { acc_s[s * (kBlock / 64) + wave] += lsum; acc_z[s * (kBlock / 64) + wave] += zeros; }
-    }
-  }
-}
-
-// COV: every set of the launch has a coverage penalty (the read set has one) and a bitmap of its own (SetDev::cov_bits): class 0
-// marks from the memo / streamed-value bodies, everything else through the set's view (with_set<true>). The host runs such a
-// launch without the capture (MultiSets::chg null): a pair finished from its set-0 result would still have to mark in set s,
-// at positions that depend on set s's layout.
-template <bool GEN, bool COV = false>
-__global__ __launch_bounds__(kBlock, 5) void paired_score_multi_kernel(PairedArgs a, MultiSets ms) {
-  __shared__ double sh_s[kBlock / 64];
-  __shared__ int sh_z[kBlock / 64];
-  // the lane-per-pair blocks keep one running sum per (set, thread) here (8 sets x 256 threads x (8 + 4) B = 24 KB);
-  // the wave-per-pair blocks stage candidates here (16 KB) and keep one running sum per (set, wave) behind them:
-  // block-uniform roles, one buffer
-  __shared__ __align__(16) unsigned char sh_raw[kMaxSets * kBlock * 12];
-  constexpr size_t kCandBytes = sizeof(int4) * (kBlock / 64) * 2 * kOvfCap;
-  static_assert(kCandBytes + kMaxSets * (kBlock / 64) * 12 <= sizeof(sh_raw), "candidate staging + per-wave sums must fit");
-  const int lb = a.total_blocks - 1 - (int)blockIdx.x;
-  // every set's thresholds per length code: read once per block (they sit in host-written device memory, a round trip
-  // each), not once per set and pair
-  __shared__ double sh_tf[kMaxSets * kTfCodes];
-  const double* tf = a.n_codes <= kTfCodes ? sh_tf : nullptr;
-  if (tf && threadIdx.x < kMaxSets * kTfCodes) {
-    const int s = threadIdx.x / kTfCodes, k = threadIdx.x % kTfCodes;
-    sh_tf[threadIdx.x] = s < ms.n && k < a.n_codes ? ms.set[s].tfloor_c[k] : 0.0;
-  }
-  if (lb < a.main_blocks) {
-    double* acc_s = (double*)sh_raw;
-    int* acc_z = (int*)(sh_raw + kMaxSets * kBlock * 8);
-    for (int s = 0; s < ms.n; s++) { acc_s[s * kBlock + threadIdx.x] = 0.0; acc_z[s * kBlock + threadIdx.x] = 0; }
-    __syncthreads();
-    const int cls = lb < a.blocks0 ? 0 : lb < a.blocks01 ? 1 : lb < a.blocks012 ? 2 : 3;
-    if ((ms.skip_classes >> cls) & 1) {  // a class of blocks left out (bit per class; set by the warm-up launch only, for bit 4 below)
-      if (threadIdx.x == 0) for (int s = 0; s < ms.n; s++) { ms.set[s].part_sum[lb] = 0.0; ms.set[s].part_zero[lb] = 0; }
-      return;
-    }
-    if (lb < a.blocks0) {
-      // (both parts of class 0 resolve every pair per set here: the lanes, pairs and order of additions are the single-set
-      // kernel's, and so are the values -- a static memo index is the index the per-call arithmetic arrives at)
-      const SlotRange rg = compact_range(a, lb);
-      // the static part streams its values like the single-set kernel (same condition as there: memo present, no coverage marks)
-      // (a penalised launch keeps streaming, as paired_score_kernel<.., COV> does)
-      const bool stat = lb < a.blocks0a && a.memo && (COV || !a.cov_bits) && a.static_val;
-      if (a.n_codes == 1) {
-        if (stat) paired_static4_multi_body<GEN, true, COV>(a, ms, rg, acc_s, acc_z, tf);
-        else paired_compact4_multi_body<GEN, true, COV>(a, ms, rg, acc_s, acc_z, tf);
-      } else {
-        __shared__ uint32_t sh_combo[256];
-        __shared__ double sh_logfloor[256];
-        for (int k = threadIdx.x; k < a.n_codes; k += kBlock) { sh_combo[k] = a.len_combo[k]; sh_logfloor[k] = a.logfloor_c[k]; }
-        const double* covthr_lds = nullptr;
-        if constexpr (COV) {  // the coverage thresholds per length code (per read set, not per path set): looked up once per pair and set
-          __shared__ double sh_covthr[256];
-          for (int k = threadIdx.x; k < a.n_codes; k += kBlock) sh_covthr[k] = a.covthr_c[k];
-          covthr_lds = sh_covthr;
-        }
-        __syncthreads();
-        PairedArgs b = a;
-        b.len_combo = sh_combo; b.logfloor_c = sh_logfloor;
-        if (COV) b.covthr_c = covthr_lds;
-        if (stat) paired_static4_multi_body<GEN, false, COV>(b, ms, rg, acc_s, acc_z, tf);
-        else paired_compact4_multi_body<GEN, false, COV>(b, ms, rg, acc_s, acc_z, tf);
-      }
-    } else if (lb < a.blocks01) paired_regs_multi_body<2, GEN, COV>(a, ms, lb, a.n0, a.n01, a.blocks0, a.blocks01, acc_s, acc_z, tf);
-    else if (lb < a.blocks012) paired_regs_multi_body<4, GEN, COV>(a, ms, lb, a.n01, a.n_main, a.blocks01, a.blocks012, acc_s, acc_z, tf);
-    else paired_delta_multi_body<GEN, COV>(a, ms, lb - a.blocks012, a.main_blocks - a.blocks012, acc_s, acc_z, tf);
-    for (int s = 0; s < ms.n; s++) {
-      double lsum = acc_s[s * kBlock + threadIdx.x];
-      int zeros = acc_z[s * kBlock + threadIdx.x];
-      block_reduce(lsum, zeros, sh_s, sh_z);
-      if (threadIdx.x == 0) { ms.set[s].part_sum[lb] = lsum; ms.set[s].part_zero[lb] = zeros; }
-      __syncthreads();  // sh_s / sh_z are reused by the next set
-    }
-    return;
-  }
-  if ((ms.skip_classes >> 4) & 1) {
-    if (threadIdx.x == 0) for (int s = 0; s < ms.n; s++) { ms.set[s].part_sum[lb] = 0.0; ms.set[s].part_zero[lb] = 0; }
-    return;
-  }
-  double* acc_s = (double*)(sh_raw + kCandBytes);
-  int* acc_z = (int*)(sh_raw + kCandBytes + kMaxSets * (kBlock / 64) * 8);
-  if (threadIdx.x < kMaxSets * (kBlock / 64)) { acc_s[threadIdx.x] = 0.0; acc_z[threadIdx.x] = 0; }
-  __syncthreads();
-  paired_overflow_multi_body<COV>(a, ms, lb - a.main_blocks, a.total_blocks - a.main_blocks, (int4(*)[2][kOvfCap])sh_raw, acc_s, acc_z, tf);
-  __syncthreads();
-  for (int s = 0; s < ms.n; s++) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double lsum = lane == 0 ? acc_s[s * (kBlock / 64) + wave] : 0.0;
-    int zeros = lane == 0 ? acc_z[s * (kBlock / 64) + wave] : 0;
-    block_reduce(lsum, zeros, sh_s, sh_z);
-    if (threadIdx.x == 0) { ms.set[s].part_sum[lb] = lsum; ms.set[s].part_zero[lb] = zeros; }
-    __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// coverage penalty sweep (graph.cc:1893-1919) over the bitmap of marked path positions.
-// A marked position p (not itself a contig start) adds p - q to bad_bases, q = previous marked
-// position of the same path, when no contig start lies in (q, p], p - q > cov_move and
-// p - (contig start before p) > mean + 5 sd.
-// ---------------------------------------------------------------------------------------
-struct CovArgs {
-  const uint32_t* bits;
-  const int* path_base;     // [n_paths+1] bit offsets (multiples of 32)
-  const int* start_off;     // [n_paths+1] into starts
-  const int* starts;        // contig start positions (path coordinates), ascending per path
-  int n_paths;
-  int total_words;
-  double cov_move;
-  double far;               // insert_mean + 5*insert_std
-  unsigned long long* bad;  // out
-};
-
-// the words of one bitmap, strided over `blocks` blocks of which this is number `block`
-__device__ __forceinline__ void coverage_sweep_words(const CovArgs& a, int block, int blocks) {
-  for (int w = block * kBlock + threadIdx.x; w < a.total_words; w += blocks * kBlock) {
-    uint32_t word = a.bits[w];
-    if (!word) continue;
-    // locate the path of this word (few paths: binary search)
-    int lo = 0, hi = a.n_paths - 1;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (a.path_base[mid] <= w * 32) lo = mid; else hi = mid - 1; }
-    const int base = a.path_base[lo], base_word = base >> 5;
-    const int* st = a.starts + a.start_off[lo];
-    const int nst = a.start_off[lo + 1] - a.start_off[lo];
-    unsigned long long local = 0;
-    uint32_t rest = word;
-    while (rest) {
-      const int b = __ffs(rest) - 1;
-      rest &= rest - 1;
-      const int p = w * 32 + b - base;
-      // previous marked position q
-      int q = -1;
-      uint32_t below = word & ((1u << b) - 1);
-      if (below) q = w * 32 + (31 - __clz(below)) - base;
-      else {
-        for (int v = w - 1; v >= base_word; v--) {
-          uint32_t x = a.bits[v];
-          if (x) { q = v * 32 + (31 - __clz(x)) - base; break; }
-        }
-      }
-      if (q < 0) continue;  // previous event is the path start (type 1)
-      // largest contig start <= p
-      int l2 = 0, h2 = nst - 1;
-      while (l2 < h2) { int mid = (l2 + h2 + 1) >> 1; if (st[mid] <= p) l2 = mid; else h2 = mid - 1; }
-      const int lb = st[l2];
-      if (lb > q) continue;  // a contig start in (q, p]: previous event has type 1 (or p is a start)
-      if ((double)(p - q) > a.cov_move && (double)(p - lb) > a.far) local += (unsigned long long)(p - q);
-    }
-    if (local) atomicAdd(a.bad, local);
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void coverage_sweep_kernel(CovArgs a) { coverage_sweep_words(a, (int)blockIdx.x, (int)gridDim.x); }
-
-// The sweeps of all path sets of a multi-set launch in ONE dispatch: blocks [block_off[s], block_off[s + 1]) sweep set s's
-// bitmap into set s's counter (a set without a bit to sweep -- the empty assembly -- has no blocks: its counter stays 0).
-struct CovMultiArgs { int n; int block_off[kMaxSets + 1]; CovArgs set[kMaxSets]; };
-__global__ __launch_bounds__(kBlock) void coverage_sweep_multi_kernel(CovMultiArgs a) {
-  int s = 0;
-  while (s + 1 < a.n && (int)blockIdx.x >= a.block_off[s + 1]) s++;
-  coverage_sweep_words(a.set[s], (int)blockIdx.x - a.block_off[s], a.block_off[s + 1] - a.block_off[s]);
-}
-// ... and their counters to where the host reads them after its wait (mapped pinned memory), n <= kMaxSets
-__global__ void store_bad_multi_kernel(const unsigned long long* bad, unsigned long long* out, int n) {
-  if (blockIdx.x == 0 && (int)threadIdx.x < n) out[threadIdx.x] = bad[threadIdx.x];
-}
-
-// ---------------------------------------------------------------------------------------
-// single-end scorer (graph.cc:1650-1743): probs_i = sum over distinct absolute positions of
-// m^e * M^(L-e); later record at the same position overwrites (graph.cc:633-644).
-// ---------------------------------------------------------------------------------------
-struct SingleArgs {
-  MateView m;
-  const int* lens;
-  const double* floor_tab;     // exp(c + k*L)
-  const double* logfloor_tab;
-  double two_T;
-  int n;
-  double* probs;
-  double* part_sum; int* part_zero; unsigned* ticket; double* out;
-  double n_reads;
-};
-
-__global__ __launch_bounds__(kBlock) void single_score_kernel(SingleArgs a) {
-  __shared__ double sh_s[kBlock / 64];
-  __shared__ int sh_z[kBlock / 64];
-  double lsum = 0.0;
-  int zeros = 0;
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock) {
-    const int4 r0 = a.m.first[i];
-    const int L = a.lens[i];
-    double acc = 0.0;
-    // One record whose window occurs at most once in the scored paths -- nearly every read of an assembly without
-    // repeats -- is its own only candidate: nothing can overwrite it (graph.cc:631-641), no second pass over the candidates.
-    bool single_cand = false;
-    if (r0.x >= 0 && ((unsigned)r0.z >> 9) == 0) {
-      const int4 o = mate_occ(a.m, r0.x);
-      if (o.z < 0) single_cand = true;  // the window is not part of the scored paths: the read scores nothing here
-      else if (o.w >= 0) { single_cand = true; const int e = r0.z & 0xff; acc = a.m.mism_pow[e] * a.m.match_pow[L - e]; }
-    }
-    if (r0.x >= 0 && !single_cand) {
-      for_each_cand(a.m, r0, [&](const Cand& x) {
-        // positions are absolute here (path index * 1e6 folded into shift); all paths share one map
-        bool live = true;
-        for_each_cand(a.m, r0, [&](const Cand& d) {
-          if (d.pos == x.pos && (d.rank > x.rank || (d.rank == x.rank && d.k > x.k))) live = false;
-        });
-        if (live) acc += a.m.mism_pow[x.edit] * a.m.match_pow[L - x.edit];
-      });
-    }
-    a.probs[i] = acc;
-    const double p = acc / a.two_T;  // GetTotalProb single (graph.cc:1526-1534)
-    if (p < a.floor_tab[L]) { zeros++; lsum += a.logfloor_tab[L]; }
-    else lsum += log(p);
-  }
-  block_reduce(lsum, zeros, sh_s, sh_z);
-  // bad_bases of the single-end scorer is identically 0 (graph.cc:1701-1733)
-  grid_finish(lsum, zeros, blockIdx.x, gridDim.x, a.part_sum, a.part_zero, a.ticket, a.out, 0.0, a.n_reads, sh_s, sh_z);
-}
-
-// ---------------------------------------------------------------------------------------
-// PacBio scorer (graph.cc:3052-3088, 3223): per read log-sum-exp over its cached alignments,
-// each counted once per occurrence of its sub-walk in the scored paths; floor; sum.
-// One WAVE per read: lanes stride over the read's records (coalesced 8-B logprob loads),
-// each lane folds its share with the reference's pairwise rule max + log1p(exp(min-max)),
-// then the 64 partial values are combined by a butterfly of the same rule.
-// ---------------------------------------------------------------------------------------
-struct PacbioArgs {
-  const int* rec_off;        // [n+1] read-major CSR
-  const int* rec_walk;       // sub-walk id per record
-  const double* rec_logp;    // log probability per record
-  const int* walk_count;     // occurrences of each sub-walk in the scored paths
-  const int* lens;
-  double floor_a, floor_b;   // log(exp(min_prob_start)), log(exp(min_prob_per_base)) (graph.cc:3075-3076)
-  int n;
-  double* logprobs;          // out: per-read log probability (-inf when no alignment)
-  double* part_sum; int* part_zero; unsigned* ticket; double* out;
-  double n_reads, bad_bases;
-};
-
-__device__ __forceinline__ double lse2(double a, double b) {  // logdouble operator+ (logdouble.hpp:37-47)
-  const double ninf = -__builtin_huge_val();
-  if (a == ninf) return b;
-  if (b == ninf) return a;
-  const double hi = fmax(a, b), lo = fmin(a, b);
-  return hi + log1p(exp(lo - hi));
-}
-
-__global__ __launch_bounds__(kBlock) void pacbio_score_kernel(PacbioArgs a) {
-  __shared__ double sh_s[kBlock / 64];
-  __shared__ int sh_z[kBlock / 64];
-  const int lane = threadIdx.x & 63;
-  const int wave_global = (blockIdx.x * kBlock + threadIdx.x) >> 6;
-  const int n_waves = (gridDim.x * kBlock) >> 6;
-  double lsum = 0.0;
-  int zeros = 0;
-  for (int i = wave_global; i < a.n; i += n_waves) {
-    const int b = a.rec_off[i], e = a.rec_off[i + 1];
-    double v = -__builtin_huge_val();
-    for (int k = b + lane; k < e; k += 64) {
-      const int c = a.walk_count[a.rec_walk[k]];
-      const double lp = a.rec_logp[k];
-      for (int t = 0; t < c; t++) v = lse2(v, lp);
-    }
-    for (int off = 32; off > 0; off >>= 1) v = lse2(v, __shfl_xor(v, off, 64));
-    if (lane == 0) {
-      a.logprobs[i] = v;
-      const double floor_lp = a.floor_a + a.floor_b * (double)a.lens[i];
-      if (v < floor_lp) { zeros++; v = floor_lp; }
-      lsum += v;
-    }
-  }
-  block_reduce(lsum, zeros, sh_s, sh_z);
-  grid_finish(lsum, zeros, blockIdx.x, gridDim.x, a.part_sum, a.part_zero, a.ticket, a.out, a.bad_bases, a.n_reads, sh_s, sh_z);
-}
-
-// The same for up to kMaxSets path sets in one pass over the records (gaml_hip_calc_prob_batch, pacbio_batch.hip.h): a
-// record's sub-walk id and log probability are loaded once, the sets' occurrence counts of that sub-walk stand side by
-// side in `counts` (32 bytes per sub-walk: two 16-byte loads). Same grid, same read-to-wave mapping, same fold order and
-// the same finishing arithmetic as pacbio_score_kernel, per set: every set's four partials are the bits a call of its own
-// would give. The per-set values live in registers: every loop over the sets is unrolled over the compile-time kMaxSets
-// with the guard s < n_sets, no array is indexed at run time.
-struct PacbioMultiArgs {
-  const int* rec_off; const int* rec_walk; const double* rec_logp;
-  const int* counts;         // [sub-walk][kMaxSets]; columns >= n_sets hold 0
-  const int* lens;
-  double floor_a, floor_b;
-  int n, n_sets;
-  double* logprobs;          // out: per-read log probability under the LAST set (what sequential calls leave there)
-  double* part_sum; int* part_zero;  // set s, block b: [s * part_stride + b]
-  int part_stride;
-  unsigned* ticket;          // kTicketWords, one ticket for all sets
-  double* out;               // set s: out[4 s ..] = {sum, floored, 0, reads}
-  double n_reads;
-};
-
-__global__ __launch_bounds__(kBlock) void pacbio_score_multi_kernel(PacbioMultiArgs a) {
-  __shared__ double sh_s[kMaxSets][kBlock / 64];
-  __shared__ int sh_z[kMaxSets][kBlock / 64];
-  __shared__ bool is_last;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wave_global = (blockIdx.x * kBlock + threadIdx.x) >> 6;
-  const int n_waves = (gridDim.x * kBlock) >> 6;
-  double lsum[kMaxSets];
-  int zeros[kMaxSets];
-#pragma unroll
-  for (int s = 0; s < kMaxSets; s++) { lsum[s] = 0.0; zeros[s] = 0; }
-  for (int i = wave_global; i < a.n; i += n_waves) {
-    const int b = a.rec_off[i], e = a.rec_off[i + 1];
-    double v[kMaxSets];
-#pragma unroll
-    for (int s = 0; s < kMaxSets; s++) v[s] = -__builtin_huge_val();
-    for (int k = b + lane; k < e; k += 64) {
-      const int4* cp = (const int4*)(a.counts + (size_t)a.rec_walk[k] * kMaxSets);
-      const int4 c0 = cp[0], c1 = cp[1];
-      const int cnt[kMaxSets] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-      const double lp = a.rec_logp[k];
-#pragma unroll
-      for (int s = 0; s < kMaxSets; s++)
-        if (s < a.n_sets) for (int t = 0; t < cnt[s]; t++) v[s] = lse2(v[s], lp);
-    }
-#pragma unroll
-    for (int s = 0; s < kMaxSets; s++)
-      if (s < a.n_sets) for (int off = 32; off > 0; off >>= 1) v[s] = lse2(v[s], __shfl_xor(v[s], off, 64));
-    if (lane == 0) {
-      const double floor_lp = a.floor_a + a.floor_b * (double)a.lens[i];
-#pragma unroll
-      for (int s = 0; s < kMaxSets; s++)
-        if (s < a.n_sets) {
-          double x = v[s];
-          if (s == a.n_sets - 1) a.logprobs[i] = x;
-          if (x < floor_lp) { zeros[s]++; x = floor_lp; }
-          lsum[s] += x;
-        }
-    }
-  }
-  // block_reduce per set, into rows of their own: one barrier for all sets
-#pragma unroll
-  for (int s = 0; s < kMaxSets; s++)
-    if (s < a.n_sets) {
-      for (int off = 32; off > 0; off >>= 1) {
-        lsum[s] += __shfl_down(lsum[s], off, 64);
-        zeros[s] += __shfl_down(zeros[s], off, 64);
-      }
-      if (lane == 0) { sh_s[s][wave] = lsum[s]; sh_z[s][wave] = zeros[s]; }
-    }
-  __syncthreads();
-  // grid_finish with ONE ticket for all sets (its `is_last` is one word: called once per set, thread 0 of the next call
-  // could overwrite it before a slow wave has read the previous value)
-  const int n_partials = (int)gridDim.x, my_slot = (int)blockIdx.x;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int s = 0; s < kMaxSets; s++)
-      if (s < a.n_sets) {
-        double ts = 0; int tz = 0;
-        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
-        __hip_atomic_store(&a.part_sum[(size_t)s * a.part_stride + my_slot], ts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&a.part_zero[(size_t)s * a.part_stride + my_slot], tz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int g = my_slot & 15;
-    const unsigned in_group = (unsigned)((n_partials - g + 15) >> 4), groups = (unsigned)min(16, n_partials);
-    bool last = false;
-    if (__hip_atomic_fetch_add(&a.ticket[1 + g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_group - 1)
-      last = __hip_atomic_fetch_add(&a.ticket[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1;
-    is_last = last;
-  }
-  __syncthreads();
-  if (!is_last) return;
-#pragma unroll
-  for (int s = 0; s < kMaxSets; s++)
-    if (s < a.n_sets) {
-      double ts = 0; int tz = 0;
-      for (int b = threadIdx.x; b < n_partials; b += kBlock) {
-        ts += __hip_atomic_load(&a.part_sum[(size_t)s * a.part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tz += __hip_atomic_load(&a.part_zero[(size_t)s * a.part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        ts += __shfl_down(ts, off, 64);
-        tz += __shfl_down(tz, off, 64);
-      }
-      if (lane == 0) { sh_s[s][wave] = ts; sh_z[s][wave] = tz; }  // (thread 0 read the rows before the barrier above)
-    }
-  __syncthreads();
-  if (threadIdx.x < kTicketWords) __hip_atomic_store(&a.ticket[threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int s = 0; s < kMaxSets; s++)
-      if (s < a.n_sets) {
-        double ts = 0; int tz = 0;
-        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
-        a.out[4 * s] = ts; a.out[4 * s + 1] = (double)tz; a.out[4 * s + 2] = 0.0; a.out[4 * s + 3] = a.n_reads;
-      }
-  }
-}
-
-// mark the slots of delta pairs in the record tables (idempotent; runs before the scoring kernel)
-__global__ __launch_bounds__(kBlock) void mark_dirty_kernel(const int* slots, int n, unsigned long long* rec8_0, int n0, int4* inl_0,
-                                                            int n01, int n_main, int4* first_0) {
-  for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) mark_dirty_slot(slots[t], rec8_0, n0, inl_0, n01, n_main, first_0);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// A batch's per-set occurrence tables, built on the device: set g = the resident tables (the path set of the
-// previous call) + the entries that changed from set to set, patches of sets 0..g applied in order. The host
-// writes only the patches (a few dozen 16-byte entries per candidate) instead of every set's whole tables.
-// ---------------------------------------------------------------------------------------------------------
-struct BatchPatch { int32_t w; uint32_t lo, hi; int32_t rank; };  // table entry w := {lo, hi, rank}
-struct BatchTabArgs {
-  const char* base;      // the resident tables
-  char* regions;         // set g at regions + g * stride, laid out like the resident tables
-  size_t stride;
-  size_t off_occ[2], bytes_occ[2], off_lo[2], bytes_lo[2], off_m[2], bytes_m[2];  // per mate; byte counts are multiples of 4
-  const BatchPatch* patches;
-  const int* patch_off;  // patches of (set g, mate mt): [patch_off[2 g + mt], patch_off[2 g + mt + 1])
-  int first;             // first set of this launch
-  int n_sets;            // sets of this launch
-  unsigned char* chg[2]; // per mate: MultiSets::chg of this launch (one byte per table entry), written by the last blocks
-  size_t chg_bytes[2];   // multiples of 16
-};
-
-__device__ __forceinline__ void block_copy_words(char* dst, const char* src, size_t bytes) {  // both 16-byte aligned
-  const size_t n16 = bytes / 16;
-  for (size_t i = threadIdx.x; i < n16; i += blockDim.x) ((int4*)dst)[i] = ((const int4*)src)[i];
-  const size_t done = n16 * 16;
-  for (size_t i = done / 4 + threadIdx.x; i < bytes / 4; i += blockDim.x) ((int*)dst)[i] = ((const int*)src)[i];
-}
-
-__global__ __launch_bounds__(1024) void batch_tables_kernel(BatchTabArgs a) {  // grid (sets of this launch + 1, 2 mates)
-  const int mt = (int)blockIdx.y;
-  if ((int)blockIdx.x == a.n_sets) {
-    // which of this launch's sets may differ from its first one, per table entry: set s differs in the entries its own
-    // patch and the patches of the sets between them name -- bits s .. n-1 for every entry of patch first + s
-    int4* z = (int4*)a.chg[mt];
-    for (size_t i = threadIdx.x; i < a.chg_bytes[mt] / 16; i += blockDim.x) z[i] = make_int4(0, 0, 0, 0);
-    __syncthreads();
-    for (int sidx = 1; sidx < a.n_sets; sidx++) {
-      const unsigned bits = (0xffu << sidx) & 0xffu;
-      for (int t = a.patch_off[2 * (a.first + sidx) + mt] + (int)threadIdx.x; t < a.patch_off[2 * (a.first + sidx) + mt + 1]; t += blockDim.x) {
-        const int w = a.patches[t].w;
-        atomicOr((unsigned*)(a.chg[mt] + (w & ~3)), bits << (8 * (w & 3)));
-      }
-    }
-    return;
-  }
-  const int g = a.first + (int)blockIdx.x;
-  char* region = a.regions + (size_t)g * a.stride;
-  block_copy_words(region + a.off_occ[mt], a.base + a.off_occ[mt], a.bytes_occ[mt]);
-  block_copy_words(region + a.off_lo[mt], a.base + a.off_lo[mt], a.bytes_lo[mt]);
-  block_copy_words(region + a.off_m[mt], a.base + a.off_m[mt], a.bytes_m[mt]);
-  int* occ = (int*)(region + a.off_occ[mt]);
-  for (int j = 0; j <= g; j++) {  // later sets override earlier ones
-    __syncthreads();
-    for (int t = a.patch_off[2 * j + mt] + (int)threadIdx.x; t < a.patch_off[2 * j + mt + 1]; t += blockDim.x) {
-      const BatchPatch pt = a.patches[t];
-      int* e = occ + 3 * (size_t)pt.w;
-      e[0] = (int)pt.lo; e[1] = (int)pt.hi; e[2] = pt.rank;
-    }
-  }
-}
-
-// bad_bases of a paired set with coverage penalty: u64 counter of the sweep -> its partial slot
-// (scale 0: a rank other than 0 of a sharded evaluation -- the all-reduce(sum) of the partials must
-// count the value once)
-__global__ void store_bad_bases_kernel(const unsigned long long* bad, double* out4, double scale) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) out4[2] = scale * (double)*bad;
-}
-
-// union of the coverage maps of all ranks: own |= maps[0] | maps[1] | ...
-__global__ __launch_bounds__(kBlock) void or_maps_kernel(uint32_t* own, const uint32_t* maps, int n_maps, int words) {
-  for (int w = blockIdx.x * kBlock + threadIdx.x; w < words; w += gridDim.x * kBlock) {
-    uint32_t v = own[w];
-    for (int k = 0; k < n_maps; k++) v |= maps[(size_t)k * words + w];
-    own[w] = v;
-  }
 }
 
 }  // namespace gaml

@@ -395,8 +395,6 @@ void paired_base_args(gaml_hip_ctx* c, PairedSet& s, PairedArgs& a, GridPlan& gp
   a.covthr_tab = a.logfloor_tab + s.logfloor_tab.size();
   a.n = (int)n;
   a.probs = s.probs.as<double>();
-  a.n_reads = (double)n;
-  a.ticket = s.red.ticket.as<unsigned>();
   const int64_t n0 = s.pt.class_count[0], n01 = n0 + s.pt.class_count[1], n_main = n01 + s.pt.class_count[2];
   a.n0 = (int)n0; a.n01 = (int)n01; a.n_main = (int)n_main;
   const int64_t n0a = s.pt.n0a, n0b = n0 - n0a;
@@ -591,7 +589,6 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   s.last_host_partials = c->host_results;
   s.last_sets = 1;
   paired_apply_set(a, sd);
-  a.out = out4;
   a.timeline = nullptr;
   const bool timeline = KNOB(c, TIMELINE) == 8;
   if (timeline) {  // in-kernel timeline (tools/kernel_timeline.py): stamps land in mapped host memory
@@ -605,14 +602,8 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   if (n > 0) {
     // HIP events bracket the dominant kernel only (bench.py's roofline; rocprofv3 must agree)
     if (c->event_timing && (c->event_tick++ % c->event_every) == 0) { if (int e = take_events(c, &ev)) return e; }
-    // 0 (FINISH_MODE = LAST_BLOCK): the block that draws the last ticket adds the partials up (two-level tickets, grid_finish: the ~1,000 blocks
-    // end together and their atomics on 17 words still take 10 us -- a finisher dispatch costs less); 1: finisher kernel
-    // (stream-ordered calls; always when a second launch shares the partials); 2: the host adds them (blocking calls)
-    int fin_mode = c->host_results ? 2 : (KNOB(c, FINISH_MODE) ? KNOB(c, FINISH_MODE) - 1 : 1);
-    // a sharded evaluation's status words are written by whatever finishes the partials on the device
-    double* status_out = nullptr;
-    if (fin_mode != 2 && c->status_dst && !c->status_done) { status_out = c->status_dst; c->status_done = true; }
-    if (fin_mode == 0) { a.status_out = status_out; a.status_a = c->status_a; a.status_b = c->status_b; }
+    // every block stores its partial; the host adds them up (blocking calls) or the finisher kernel does (stream-ordered calls)
+    const bool finisher = !c->host_results;
     s.last_total_blocks = n_partials;
     const dim3 grid(a.total_blocks), block(kBlock);
     // Timed launches attach the two events to the dispatch itself (hipExtLaunchKernelGGL: the events carry
@@ -622,17 +613,19 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     hipEvent_t e0 = ev ? ev->first : nullptr, e1 = ev ? ev->second : nullptr;
 #define GAML_LAUNCH_SCORE(...) hipExtLaunchKernelGGL((paired_score_kernel<__VA_ARGS__>), grid, block, KNOB(c, SCORE_LDS_BYTES), st, e0, e1, 0, a)
 #ifdef GAML_HIP_DEV
-    if (timeline) GAML_LAUNCH_SCORE(false, false, true);  // (the instantiation with in-kernel stamps: development builds only)
+    if (timeline) GAML_LAUNCH_SCORE(false, true);  // (the instantiation with in-kernel stamps: development builds only)
     else
 #endif
-    if (gen_set) { if (fin_mode) GAML_LAUNCH_SCORE(false, true); else GAML_LAUNCH_SCORE(true, true); }
+    if (gen_set) GAML_LAUNCH_SCORE(true);
     // a penalised set (no repeated windows, memo present): class 0 marks from the memo / streamed-value bodies
-    else if (cov && a.memo && KNOB(c, NO_COV_INSTANCE) == 0) { if (fin_mode) GAML_LAUNCH_SCORE(false, false, false, true); else GAML_LAUNCH_SCORE(true, false, false, true); }
-    else if (fin_mode) GAML_LAUNCH_SCORE(false, false);
-    else GAML_LAUNCH_SCORE(true, false);
+    else if (cov && a.memo && KNOB(c, NO_COV_INSTANCE) == 0) GAML_LAUNCH_SCORE(false, false, true);
+    else GAML_LAUNCH_SCORE(false);
 #undef GAML_LAUNCH_SCORE
     HIP_TRY(c, hipGetLastError());
-    if (fin_mode == 1) {
+    if (finisher) {
+      // a sharded evaluation's status words ride with the finisher (the one kernel that writes them): no dispatch of their own
+      double* status_out = nullptr;
+      if (c->status_dst && !c->status_done) { status_out = c->status_dst; c->status_done = true; }
       hipLaunchKernelGGL(finish_partials_kernel, dim3(1), dim3(kBlock), 0, st, a.part_sum, a.part_zero, n_partials, out4, cov ? -1.0 : 0.0, (double)n, status_out, c->status_a, c->status_b);
       HIP_TRY(c, hipGetLastError());
     }

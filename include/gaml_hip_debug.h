@@ -72,7 +72,7 @@ int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int
 enum gaml_hip_knob {
   GAML_HIP_KNOB_GRID_CAP_COMPACT = 0,       /* n > 0: most blocks of the compact class (default: from the device's CU count) */
   GAML_HIP_KNOB_SCORE_LDS_BYTES = 1,        /* n: dynamic LDS bytes on the single-set scoring launch (occupancy experiments) */
-  GAML_HIP_KNOB_FINISH_MODE = 2,            /* gaml_hip_finish_mode: who adds the partials of a stream-ordered call (default: the finisher kernel) */
+  GAML_HIP_KNOB_FINISH_MODE = 2,            /* retired, setting it has no effect (it chose the last-block finish route of the paired scoring kernels, which is removed) */
   GAML_HIP_KNOB_TIMELINE = 3,               /* 8: in-kernel time stamps (gaml_hip_debug_timeline); any non-zero value keeps batches off the multi-set kernel */
   GAML_HIP_KNOB_NO_MEMO = 4,                /* 1: no floor/log memo of pair terms */
   GAML_HIP_KNOB_ALIGNER_ROUTE = 5,          /* gaml_hip_aligner_route: which route the window aligner is held to (default: its own choice per batch) */
@@ -100,10 +100,6 @@ enum gaml_hip_knob {
   GAML_HIP_KNOB_COUNT = 27
 };
 /* the values of the knobs that choose between routes (0 = the default, in every one) */
-enum gaml_hip_finish_mode {
-  GAML_HIP_FINISH_LAST_BLOCK = 1,  /* the block that draws the last ticket adds the partials up (two-level tickets in the kernel) */
-  GAML_HIP_FINISH_KERNEL = 2       /* a finisher kernel does: the default, spelled out */
-};
 enum gaml_hip_aligner_route {
   GAML_HIP_ALIGNER_HOST = 1,         /* the host aligner */
   GAML_HIP_ALIGNER_HOST_SORT = 2,    /* the hits of large batches sorted on the host */

@@ -34,10 +34,10 @@ def test_every_declared_symbol_is_exported(built):
     assert not [n for n in names if n not in release], [n for n in names if n not in release]
     assert not [n for n in names + dbg if n not in dev], [n for n in names + dbg if n not in dev]
     assert not [n for n in release if "debug" in n], [n for n in release if "debug" in n]
-    # ... and no kernel instantiation with in-kernel time stamps (paired_score_kernel<false, false, true>) in the product
+    # ... and no kernel instantiation with in-kernel time stamps (paired_score_kernel<false, true>: GEN, TL, COV) in the product
     blob = open(os.path.join(ROOT, "gaml_amd", "libgaml_hip.so"), "rb").read()
-    assert b"paired_score_kernelILb0ELb0ELb1E" not in blob
-    assert b"paired_score_kernelILb0ELb0ELb1E" in open(os.path.join(ROOT, "gaml_amd", "libgaml_hip_dev.so"), "rb").read()
+    assert b"paired_score_kernelILb0ELb1ELb0E" not in blob
+    assert b"paired_score_kernelILb0ELb1ELb0E" in open(os.path.join(ROOT, "gaml_amd", "libgaml_hip_dev.so"), "rb").read()
     lib = ctypes.CDLL(os.path.join(ROOT, "gaml_amd", "libgaml_hip.so"))
     assert not [n for n in names if not hasattr(lib, n)]
 
@@ -133,7 +133,7 @@ def test_knob_registry_matches_the_binding_and_keeps_its_numbers(built):
     assert {k.name: int(k) for k in api.Knob} == knobs and len(api.Knob.__members__) == len(knobs)  # (no alias either)
     assert sorted(knobs.values()) == list(range(count)) and api.KNOB_COUNT == count
     assert [api.Knob(i).name for i in range(25)] == KNOBS_0_TO_24
-    values = {"gaml_hip_finish_mode": ("GAML_HIP_FINISH_", api.FinishMode), "gaml_hip_aligner_route": ("GAML_HIP_ALIGNER_", api.AlignerRoute),
+    values = {"gaml_hip_aligner_route": ("GAML_HIP_ALIGNER_", api.AlignerRoute),
               "gaml_hip_delta_policy": ("GAML_HIP_DELTA_", api.DeltaPolicy), "gaml_hip_upload_route": ("GAML_HIP_UPLOAD_", api.UploadRoute),
               "gaml_hip_batch_route": ("GAML_HIP_BATCH_", api.BatchRoute)}
     assert set(enums) == set(values) | {"gaml_hip_knob"}
