@@ -327,6 +327,10 @@ def _load():
         L.gaml_hip_debug_timeline.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64]
     if hasattr(L, "gaml_hip_pacbio_stats"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_pacbio_stats.argtypes = [vp, C.c_int, _i64p]
+    if hasattr(L, "gaml_hip_single_stats"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_single_stats.argtypes = [vp, C.c_int, _i64p]
+        L.gaml_hip_set_single_onepass.argtypes = [vp, C.c_int32]
+        L.gaml_hip_get_single_onepass.argtypes = [vp]
     L.gaml_hip_last_phases.argtypes = [vp, _f64p]
     L.gaml_hip_table_stats.argtypes = [vp, C.c_int, _i64p]
     L.gaml_hip_aligner_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -678,6 +682,16 @@ class Context:
     def gap_penalty_device(self) -> bool:
         return hasattr(_lib, "gaml_hip_get_gap_penalty_device") and _lib.gaml_hip_get_gap_penalty_device(self._h) == 1
 
+    def set_single_onepass(self, on):
+        """Let single-end sets go along on calc_prob_batch's one-pass routes (gaml_hip_set_single_onepass); off by default, or
+        what GAML_HIP_SINGLE_BATCH=onepass said when the context was made. Same values either way."""
+        if not hasattr(_lib, "gaml_hip_set_single_onepass"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_set_single_onepass")
+        self._check(_lib.gaml_hip_set_single_onepass(self._h, 1 if on else 0))
+
+    def single_onepass(self) -> bool:
+        return hasattr(_lib, "gaml_hip_get_single_onepass") and _lib.gaml_hip_get_single_onepass(self._h) == 1
+
     def calc_partials(self, paths):
         flat, offs = _flat(paths)
         tl = C.c_int32()
@@ -908,6 +922,16 @@ class Context:
         out = np.zeros(4, np.int64)
         self._check(_lib.gaml_hip_pacbio_stats(self._h, rs, out))
         return {"subwalks": int(out[0]), "records": int(out[1]), "misses": int(out[2]), "multi_launches": int(out[3])}
+
+    def single_stats(self, rs):
+        """{windows, records, table_bytes, multi_launches} of a single-end set (gaml_hip_single_stats): windows registered,
+        records in the read-major table, bytes of occurrence tables staged by the last call or chunk, batch chunks scored in
+        one multi-set launch."""
+        if not hasattr(_lib, "gaml_hip_single_stats"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_single_stats")
+        out = np.zeros(4, np.int64)
+        self._check(_lib.gaml_hip_single_stats(self._h, rs, out))
+        return {"windows": int(out[0]), "records": int(out[1]), "table_bytes": int(out[2]), "multi_launches": int(out[3])}
 
     def aligner_stats(self):
         w, k, us = C.c_int64(), C.c_int64(), C.c_double()

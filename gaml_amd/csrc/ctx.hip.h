@@ -403,6 +403,14 @@ struct PairedSet {
   AdviceDev adv;
 };
 
+// a single-end set's side of gaml_hip_calc_prob_batch (single_batch.hip.h)
+struct SgMulti {
+  DevBuf part_sum, part_zero, ticket;  // per set and block; a ticket of its own (single_score_multi_kernel)
+  PinBuf out;       // {sum, floored, 0, reads} per set, written by the last block
+  int64_t launches = 0;
+  void release() { part_sum.release(); part_zero.release(); ticket.release(); out.release(); }
+};
+
 struct SingleSet {
   gaml_single_cfg cfg;
   ShortMate mate;
@@ -414,6 +422,8 @@ struct SingleSet {
   std::vector<double> floor_tab, logfloor_tab;
   bool tabs_uploaded = false;
   Staging stage;
+  SgMulti multi;
+  int64_t table_bytes = 0;  // occurrence tables staged by the last call or chunk (gaml_hip_single_stats)
 };
 
 struct DpDev {  // device buffers of the PacBio banded DP
@@ -496,6 +506,8 @@ struct SetRef { int kind, idx; };
 
 // GAML_HIP_GAP_PENALTY=device: what a new context's gap_penalty_device starts as (read when the context is made)
 inline bool gap_penalty_env() { const char* e = getenv("GAML_HIP_GAP_PENALTY"); return e && strcmp(e, "device") == 0; }
+// GAML_HIP_SINGLE_BATCH=onepass: what a new context's single_onepass starts as (read when the context is made)
+inline bool single_onepass_env() { const char* e = getenv("GAML_HIP_SINGLE_BATCH"); return e && strcmp(e, "onepass") == 0; }
 
 }  // namespace detail
 }  // namespace gaml
@@ -554,6 +566,7 @@ struct gaml_hip_ctx {
   // fallback, device passes}, and the path set with the base length in its gap (kept from call to call)
   int64_t gap_stats[4] = {0, 0, 0, 0};
   bool gap_penalty_device = gap_penalty_env();  // penalised paired sets may take the gap profile's device route (gaml_hip_set_gap_penalty_device)
+  bool single_onepass = single_onepass_env();  // single-end sets go along on the batch's one-pass routes (gaml_hip_set_single_onepass)
   std::vector<int32_t> gap_flat;
   std::vector<int64_t> gap_offs;
   // evaluation in progress (between eval_begin and eval_finish)

@@ -232,6 +232,7 @@ std::vector<Walk> unflatten(const int32_t* flat, const int64_t* offs, int32_t n)
 namespace {
 
 #include "single_launch.hip.h"
+#include "single_batch.hip.h"
 #include "pacbio_launch.hip.h"
 #include "pacbio_batch.hip.h"
 #include "aligner_launch.hip.h"
@@ -507,7 +508,7 @@ void gaml_hip_destroy(gaml_hip_ctx* c) {
     (void)hipDeviceSynchronize();
     if (c->comm) { gaml::comm_destroy(c->comm); c->comm = nullptr; }
     auto drop_stage = [](Staging& s) { for (int k = 0; k < kRing; k++) { s.host[k].release(); if (s.done[k]) (void)hipEventDestroy(s.done[k]); } };
-    for (auto& s : c->singles) { s->dev.first.release(); s->dev.extra.release(); s->dev.pows.release(); s->lens.release(); s->probs.release(); s->tabs.release(); s->occ_arena.release(); s->red.release(); drop_stage(s->stage); }
+    for (auto& s : c->singles) { s->dev.first.release(); s->dev.extra.release(); s->dev.pows.release(); s->lens.release(); s->probs.release(); s->tabs.release(); s->occ_arena.release(); s->red.release(); s->multi.release(); drop_stage(s->stage); }
     for (auto& s : c->paireds) {
       if (s->rebuild.stream) (void)hipStreamDestroy(s->rebuild.stream);
       if (s->rebuild.done) (void)hipEventDestroy(s->rebuild.done);
@@ -1447,6 +1448,21 @@ int gaml_hip_pacbio_stats(gaml_hip_ctx* c, int rs, int64_t* out4) {
   out4[0] = (int64_t)s.recs.size(); out4[1] = nrec; out4[2] = s.misses; out4[3] = s.multi.launches;
   return GAML_HIP_OK;
 }
+
+int gaml_hip_single_stats(gaml_hip_ctx* c, int rs, int64_t* out4) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 0 || !out4) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const SingleSet& s = *c->singles[c->handles[rs].idx];
+  out4[0] = (int64_t)s.mate.wins.size(); out4[1] = s.mate.active_records; out4[2] = s.table_bytes; out4[3] = s.multi.launches;
+  return GAML_HIP_OK;
+}
+
+int gaml_hip_set_single_onepass(gaml_hip_ctx* c, int32_t on) {
+  if (!c) return GAML_HIP_EINVAL;
+  c->single_onepass = on != 0;  // (a multi-device or rank-per-process context only keeps the flag: its batches take other ways)
+  return GAML_HIP_OK;
+}
+int gaml_hip_get_single_onepass(const gaml_hip_ctx* c) { return c && c->single_onepass ? 1 : 0; }
 
 int gaml_hip_last_phases(gaml_hip_ctx* c, double* out8) {
   if (!c || !out8) return GAML_HIP_EINVAL;

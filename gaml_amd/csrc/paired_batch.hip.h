@@ -1,4 +1,4 @@
-// paired_batch.hip.h -- gaml_hip_calc_prob_batch over paired and PacBio sets: per-set tables from patches / whole, one pass over the records
+// paired_batch.hip.h -- gaml_hip_calc_prob_batch over paired, PacBio and (opt-in) single-end sets: per-set tables from patches / whole, one pass over the records
 // (one translation unit with gaml_hip.hip, which includes this file at the place its contents used to stand)
 //
 //   batch_fast_capable    may this context's batches take the one-pass routes at all
@@ -11,16 +11,18 @@
 // ---------------------------------------------------------------------------------------------------------
 // gaml_hip_calc_prob_batch, fast path: up to kMaxSets path sets in ONE pass over the records of every paired set
 // (paired_score_multi_kernel). The host plans the sets one after the other straight into consecutive regions of one
-// arena slot; then one launch per read set, one wait. Contexts with single-end sets or without a memo take the
+// arena slot; then one launch per read set, one wait. Contexts with single-end sets (switch off) or without a memo take the
 // sequential path of gaml_hip_calc_prob_batch (same results). A set with a coverage penalty goes along: its path sets mark into bitmaps of their
 // own, one sweep dispatch per launch (launch_paired_multi); the wait is then a real stream wait, one per chunk.
 // PacBio sets without a coverage penalty go along as well, beside the paired sets or on their own: one dispatch of
 // pacbio_score_multi_kernel per set and chunk, enqueued before the paired sets are planned (pacbio_batch.hip.h); the wait is
-// a stream wait then too. A PacBio set with a penalty keeps the whole context on the sequential path.
+// a stream wait then too. A PacBio set with a penalty keeps the whole context on the sequential path. So does a single-end
+// set, unless the context's switch is on (gaml_hip_set_single_onepass, off by default): then single-end sets go along the
+// same way, one dispatch of single_score_multi_kernel per set and chunk, enqueued behind the PacBio one (single_batch.hip.h).
 // ---------------------------------------------------------------------------------------------------------
 static bool batch_fast_capable(const gaml_hip_ctx* c) {
   if (c->handles.empty() || KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_SEQUENTIAL) return false;  // force the sequential path (A/B, tools/)
-  for (auto& h : c->handles) if (h.kind == 0) return false;
+  if (!c->single_onepass) for (auto& h : c->handles) if (h.kind == 0) return false;  // single-end sets go along only where the context says so (single_batch.hip.h)
   for (auto& pb : c->pacbios) if (pb->cfg.penalty_constant > 0) return false;
   for (auto& ps : c->paireds) if (!paired_multi_capable(c, *ps)) return false;
   return true;
@@ -170,6 +172,8 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
   };
   PbChunk pb(c);
   if (int e = pacbio_chunk_launch(c, pb, n, paths, offs, set_offs)) return e;
+  SgChunk sg(c);
+  if (int e = single_chunk_launch(c, sg, n, paths, offs, set_offs)) return e;
   for (int k = 0; k < n; k++) {
     int64_t pending = 0;
     if (int e = eval_begin(c, paths, offs + set_offs[k], set_offs[k + 1] - set_offs[k], &pending)) return e;
@@ -227,7 +231,8 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
   _mm_sfence();
   for (size_t i = 0; i < nps; i++) c->paireds[i]->batches_patched++;
   multi_collect(c, n, partials_out, true);
-  return pacbio_chunk_collect(c, pb, n, partials_out);
+  if (int e = pacbio_chunk_collect(c, pb, n, partials_out)) return e;
+  return single_chunk_collect(c, sg, n, partials_out);
 }
 
 // A chunk with whole tables per set, packed by the host into the regions. Returns 1 when a set's tables did not fit the
@@ -267,6 +272,8 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
   };
   PbChunk pb(c);
   if (int e = pacbio_chunk_launch(c, pb, n, paths, offs, set_offs)) return e;
+  SgChunk sg(c);
+  if (int e = single_chunk_launch(c, sg, n, paths, offs, set_offs)) return e;
   for (int k = 0; k < n; k++) {
     int64_t pending = 0;
     if (int e = eval_begin(c, paths, offs + set_offs[k], set_offs[k + 1] - set_offs[k], &pending)) return e;
@@ -290,6 +297,7 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
   if (int e = multi_wait(c)) return e;
   for (size_t i = 0; i < nps; i++) c->paireds[i]->batches_full++;
   multi_collect(c, n, partials_out, true);
-  return pacbio_chunk_collect(c, pb, n, partials_out);
+  if (int e = pacbio_chunk_collect(c, pb, n, partials_out)) return e;
+  return single_chunk_collect(c, sg, n, partials_out);
 }
 

@@ -94,6 +94,31 @@ struct SingleArgs {
   double n_reads;
 };
 
+// One read under one path set's occurrence tables: the sum over its live candidates of m^e * M^(L-e). Shared by
+// single_score_kernel and single_score_multi_kernel (same arithmetic in the same order: same bits).
+__device__ __forceinline__ double single_read_acc(const MateView& m, const int4& r0, int L) {
+  double acc = 0.0;
+  // One record whose window occurs at most once in the scored paths -- nearly every read of an assembly without
+  // repeats -- is its own only candidate: nothing can overwrite it (graph.cc:631-641), no second pass over the candidates.
+  bool single_cand = false;
+  if (r0.x >= 0 && ((unsigned)r0.z >> 9) == 0) {
+    const int4 o = mate_occ(m, r0.x);
+    if (o.z < 0) single_cand = true;  // the window is not part of the scored paths: the read scores nothing here
+    else if (o.w >= 0) { single_cand = true; const int e = r0.z & 0xff; acc = m.mism_pow[e] * m.match_pow[L - e]; }
+  }
+  if (r0.x >= 0 && !single_cand) {
+    for_each_cand(m, r0, [&](const Cand& x) {
+      // positions are absolute here (path index * 1e6 folded into shift); all paths share one map
+      bool live = true;
+      for_each_cand(m, r0, [&](const Cand& d) {
+        if (d.pos == x.pos && (d.rank > x.rank || (d.rank == x.rank && d.k > x.k))) live = false;
+      });
+      if (live) acc += m.mism_pow[x.edit] * m.match_pow[L - x.edit];
+    });
+  }
+  return acc;
+}
+
 __global__ __launch_bounds__(kBlock) void single_score_kernel(SingleArgs a) {
   __shared__ double sh_s[kBlock / 64];
   __shared__ int sh_z[kBlock / 64];
@@ -102,25 +127,7 @@ __global__ __launch_bounds__(kBlock) void single_score_kernel(SingleArgs a) {
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock) {
     const int4 r0 = a.m.first[i];
     const int L = a.lens[i];
-    double acc = 0.0;
-    // One record whose window occurs at most once in the scored paths -- nearly every read of an assembly without
-    // repeats -- is its own only candidate: nothing can overwrite it (graph.cc:631-641), no second pass over the candidates.
-    bool single_cand = false;
-    if (r0.x >= 0 && ((unsigned)r0.z >> 9) == 0) {
-      const int4 o = mate_occ(a.m, r0.x);
-      if (o.z < 0) single_cand = true;  // the window is not part of the scored paths: the read scores nothing here
-      else if (o.w >= 0) { single_cand = true; const int e = r0.z & 0xff; acc = a.m.mism_pow[e] * a.m.match_pow[L - e]; }
-    }
-    if (r0.x >= 0 && !single_cand) {
-      for_each_cand(a.m, r0, [&](const Cand& x) {
-        // positions are absolute here (path index * 1e6 folded into shift); all paths share one map
-        bool live = true;
-        for_each_cand(a.m, r0, [&](const Cand& d) {
-          if (d.pos == x.pos && (d.rank > x.rank || (d.rank == x.rank && d.k > x.k))) live = false;
-        });
-        if (live) acc += a.m.mism_pow[x.edit] * a.m.match_pow[L - x.edit];
-      });
-    }
+    const double acc = single_read_acc(a.m, r0, L);
     a.probs[i] = acc;
     const double p = acc / a.two_T;  // GetTotalProb single (graph.cc:1526-1534)
     if (p < a.floor_tab[L]) { zeros++; lsum += a.logfloor_tab[L]; }
@@ -187,6 +194,75 @@ __global__ __launch_bounds__(kBlock) void pacbio_score_kernel(PacbioArgs a) {
   grid_finish(lsum, zeros, blockIdx.x, gridDim.x, a.part_sum, a.part_zero, a.ticket, a.out, a.bad_bases, a.n_reads, sh_s, sh_z);
 }
 
+// The end of a multi-set scoring kernel (pacbio_score_multi_kernel, single_score_multi_kernel): block_reduce and grid_finish
+// per set, in their order, with rows of partials of the sets' own (set s, block b: [s * part_stride + b]) and ONE ticket for
+// all sets; out[4 s ..] = {sum, floored, 0, reads}. Every loop over the sets is unrolled over kMaxSets: lsum / zeros stay
+// in registers.
+__device__ __forceinline__ void multi_grid_finish(double (&lsum)[kMaxSets], int (&zeros)[kMaxSets], int n_sets, double* part_sum, int* part_zero,
+                                                  int part_stride, unsigned* ticket, double* out, double n_reads,
+                                                  double (&sh_s)[kMaxSets][kBlock / 64], int (&sh_z)[kMaxSets][kBlock / 64]) {
+  __shared__ bool is_last;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // block_reduce per set, into rows of their own: one barrier for all sets
+#pragma unroll
+  for (int s = 0; s < kMaxSets; s++)
+    if (s < n_sets) {
+      for (int off = 32; off > 0; off >>= 1) {
+        lsum[s] += __shfl_down(lsum[s], off, 64);
+        zeros[s] += __shfl_down(zeros[s], off, 64);
+      }
+      if (lane == 0) { sh_s[s][wave] = lsum[s]; sh_z[s][wave] = zeros[s]; }
+    }
+  __syncthreads();
+  // grid_finish with ONE ticket for all sets (its `is_last` is one word: called once per set, thread 0 of the next call
+  // could overwrite it before a slow wave has read the previous value)
+  const int n_partials = (int)gridDim.x, my_slot = (int)blockIdx.x;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int s = 0; s < kMaxSets; s++)
+      if (s < n_sets) {
+        double ts = 0; int tz = 0;
+        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
+        __hip_atomic_store(&part_sum[(size_t)s * part_stride + my_slot], ts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&part_zero[(size_t)s * part_stride + my_slot], tz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int g = my_slot & 15;
+    const unsigned in_group = (unsigned)((n_partials - g + 15) >> 4), groups = (unsigned)min(16, n_partials);
+    bool last = false;
+    if (__hip_atomic_fetch_add(&ticket[1 + g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_group - 1)
+      last = __hip_atomic_fetch_add(&ticket[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1;
+    is_last = last;
+  }
+  __syncthreads();
+  if (!is_last) return;
+#pragma unroll
+  for (int s = 0; s < kMaxSets; s++)
+    if (s < n_sets) {
+      double ts = 0; int tz = 0;
+      for (int b = threadIdx.x; b < n_partials; b += kBlock) {
+        ts += __hip_atomic_load(&part_sum[(size_t)s * part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tz += __hip_atomic_load(&part_zero[(size_t)s * part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        ts += __shfl_down(ts, off, 64);
+        tz += __shfl_down(tz, off, 64);
+      }
+      if (lane == 0) { sh_s[s][wave] = ts; sh_z[s][wave] = tz; }  // (thread 0 read the rows before the barrier above)
+    }
+  __syncthreads();
+  if (threadIdx.x < kTicketWords) __hip_atomic_store(&ticket[threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int s = 0; s < kMaxSets; s++)
+      if (s < n_sets) {
+        double ts = 0; int tz = 0;
+        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
+        out[4 * s] = ts; out[4 * s + 1] = (double)tz; out[4 * s + 2] = 0.0; out[4 * s + 3] = n_reads;
+      }
+  }
+}
+
 // The same for up to kMaxSets path sets in one pass over the records (gaml_hip_calc_prob_batch, pacbio_batch.hip.h): a
 // record's sub-walk id and log probability are loaded once, the sets' occurrence counts of that sub-walk stand side by
 // side in `counts` (32 bytes per sub-walk: two 16-byte loads). Same grid, same read-to-wave mapping, same fold order and
@@ -210,8 +286,7 @@ struct PacbioMultiArgs {
 __global__ __launch_bounds__(kBlock) void pacbio_score_multi_kernel(PacbioMultiArgs a) {
   __shared__ double sh_s[kMaxSets][kBlock / 64];
   __shared__ int sh_z[kMaxSets][kBlock / 64];
-  __shared__ bool is_last;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int wave_global = (blockIdx.x * kBlock + threadIdx.x) >> 6;
   const int n_waves = (gridDim.x * kBlock) >> 6;
   double lsum[kMaxSets];
@@ -247,64 +322,56 @@ __global__ __launch_bounds__(kBlock) void pacbio_score_multi_kernel(PacbioMultiA
         }
     }
   }
-  // block_reduce per set, into rows of their own: one barrier for all sets
+  multi_grid_finish(lsum, zeros, a.n_sets, a.part_sum, a.part_zero, a.part_stride, a.ticket, a.out, a.n_reads, sh_s, sh_z);
+}
+
+// The single-end scorer for up to kMaxSets path sets in one pass over the read-major records (gaml_hip_calc_prob_batch,
+// single_batch.hip.h): a read's first record and length are loaded once; every set brings occurrence tables of its own (the
+// three pointers of a MateView, into one arena) and its 2T. The record table holds the windows of ALL sets of the chunk: a
+// window a set does not name reads as absent in that set's table and is skipped, the candidates that remain keep their
+// (record, occurrence) order, so single_read_acc adds the terms a launch of single_score_kernel for that set alone adds,
+// in its order. Same grid and read-to-thread mapping; finished like pacbio_score_multi_kernel. The rule of that kernel
+// holds here too: per-set pointers are fixed arrays of kMaxSets in the arguments, every loop over the sets is unrolled over
+// the compile-time kMaxSets with the guard s < n_sets, no array is indexed at run time.
+struct SingleMultiArgs {
+  const int4* first; const int4* extra;             // MateView: what does not depend on the path set
+  const double* mism_pow; const double* match_pow;
+  const int* lens;
+  const double* floor_tab; const double* logfloor_tab;
+  int n, n_sets;
+  const int4* occ[kMaxSets]; const int* multi_off[kMaxSets]; const int4* multi[kMaxSets];  // MateView: set s's tables
+  double two_T[kMaxSets];
+  double* probs;             // out: per-read value under the LAST set (what sequential calls leave there)
+  double* part_sum; int* part_zero;  // set s, block b: [s * part_stride + b]
+  int part_stride;
+  unsigned* ticket;          // kTicketWords, one ticket for all sets
+  double* out;               // set s: out[4 s ..] = {sum, floored, 0, reads} (bad_bases is identically 0: single_score_kernel)
+  double n_reads;
+};
+
+__global__ __launch_bounds__(kBlock) void single_score_multi_kernel(SingleMultiArgs a) {
+  __shared__ double sh_s[kMaxSets][kBlock / 64];
+  __shared__ int sh_z[kMaxSets][kBlock / 64];
+  double lsum[kMaxSets];
+  int zeros[kMaxSets];
 #pragma unroll
-  for (int s = 0; s < kMaxSets; s++)
-    if (s < a.n_sets) {
-      for (int off = 32; off > 0; off >>= 1) {
-        lsum[s] += __shfl_down(lsum[s], off, 64);
-        zeros[s] += __shfl_down(zeros[s], off, 64);
-      }
-      if (lane == 0) { sh_s[s][wave] = lsum[s]; sh_z[s][wave] = zeros[s]; }
-    }
-  __syncthreads();
-  // grid_finish with ONE ticket for all sets (its `is_last` is one word: called once per set, thread 0 of the next call
-  // could overwrite it before a slow wave has read the previous value)
-  const int n_partials = (int)gridDim.x, my_slot = (int)blockIdx.x;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int s = 0; s < kMaxSets; s++)
-      if (s < a.n_sets) {
-        double ts = 0; int tz = 0;
-        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
-        __hip_atomic_store(&a.part_sum[(size_t)s * a.part_stride + my_slot], ts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&a.part_zero[(size_t)s * a.part_stride + my_slot], tz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int g = my_slot & 15;
-    const unsigned in_group = (unsigned)((n_partials - g + 15) >> 4), groups = (unsigned)min(16, n_partials);
-    bool last = false;
-    if (__hip_atomic_fetch_add(&a.ticket[1 + g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_group - 1)
-      last = __hip_atomic_fetch_add(&a.ticket[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1;
-    is_last = last;
-  }
-  __syncthreads();
-  if (!is_last) return;
-#pragma unroll
-  for (int s = 0; s < kMaxSets; s++)
-    if (s < a.n_sets) {
-      double ts = 0; int tz = 0;
-      for (int b = threadIdx.x; b < n_partials; b += kBlock) {
-        ts += __hip_atomic_load(&a.part_sum[(size_t)s * a.part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tz += __hip_atomic_load(&a.part_zero[(size_t)s * a.part_stride + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        ts += __shfl_down(ts, off, 64);
-        tz += __shfl_down(tz, off, 64);
-      }
-      if (lane == 0) { sh_s[s][wave] = ts; sh_z[s][wave] = tz; }  // (thread 0 read the rows before the barrier above)
-    }
-  __syncthreads();
-  if (threadIdx.x < kTicketWords) __hip_atomic_store(&a.ticket[threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (threadIdx.x == 0) {
+  for (int s = 0; s < kMaxSets; s++) { lsum[s] = 0.0; zeros[s] = 0; }
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock) {
+    const int4 r0 = a.first[i];
+    const int L = a.lens[i];
+    const double floor_p = a.floor_tab[L], floor_lp = a.logfloor_tab[L];
 #pragma unroll
     for (int s = 0; s < kMaxSets; s++)
       if (s < a.n_sets) {
-        double ts = 0; int tz = 0;
-        for (int w = 0; w < kBlock / 64; w++) { ts += sh_s[s][w]; tz += sh_z[s][w]; }
-        a.out[4 * s] = ts; a.out[4 * s + 1] = (double)tz; a.out[4 * s + 2] = 0.0; a.out[4 * s + 3] = a.n_reads;
+        const MateView m{a.first, a.extra, a.occ[s], nullptr, a.multi_off[s], a.multi[s], a.mism_pow, a.match_pow};
+        const double acc = single_read_acc(m, r0, L);
+        if (s == a.n_sets - 1) a.probs[i] = acc;
+        const double p = acc / a.two_T[s];  // GetTotalProb single (graph.cc:1526-1534)
+        if (p < floor_p) { zeros[s]++; lsum[s] += floor_lp; }
+        else lsum[s] += log(p);
       }
   }
+  multi_grid_finish(lsum, zeros, a.n_sets, a.part_sum, a.part_zero, a.part_stride, a.ticket, a.out, a.n_reads, sh_s, sh_z);
 }
 
 // ---------------------------------------------------------------------------------------------------------

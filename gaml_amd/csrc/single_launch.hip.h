@@ -1,5 +1,6 @@
 // single_launch.hip.h -- single-end read sets: host preparation and launch (CalcScoreForPaths graph.cc:1650-1743)
-// (one translation unit with gaml_hip.hip, which includes this file at the place its contents used to stand)
+// (one translation unit with gaml_hip.hip, which includes this file at the place its contents used to stand; the batch
+// side -- several path sets per launch -- is single_batch.hip.h, included behind this file)
 #pragma once
 
 // ---------------------------------------------------------------------------------------
@@ -26,24 +27,29 @@ int32_t prepare_single_host(gaml_hip_ctx* c, SingleSet& s, const std::vector<Wal
   return tl;
 }
 
-int launch_single(gaml_hip_ctx* c, SingleSet& s, const std::vector<Walk>& paths, int32_t total_len, hipStream_t st, double* out4) {
-  if (!s.tabs_uploaded) {
-    const int lmax = s.mate.max_len;
-    s.floor_tab.resize(lmax + 1); s.logfloor_tab.resize(lmax + 1);
-    for (int v = 0; v <= lmax; v++) {
-      s.floor_tab[v] = std::exp(s.cfg.min_prob_start + s.cfg.min_prob_per_base * v);  // graph.cc:1528
-      s.logfloor_tab[v] = std::log(s.floor_tab[v]);
-    }
-    HIP_TRY(c, s.tabs.reserve(2 * (size_t)(lmax + 1) * sizeof(double)));
-    HIP_TRY(c, hipMemcpy(s.tabs.p, s.floor_tab.data(), (lmax + 1) * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(s.tabs.as<double>() + lmax + 1, s.logfloor_tab.data(), (lmax + 1) * sizeof(double), hipMemcpyHostToDevice));
-    const int64_t n = s.mate.n_local();
-    HIP_TRY(c, s.lens.reserve(std::max<size_t>(1, n) * sizeof(int32_t)));
-    if (n) HIP_TRY(c, hipMemcpy(s.lens.p, s.mate.lens.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, s.probs.reserve(std::max<size_t>(1, n) * sizeof(double)));
-    HIP_TRY(c, s.red.init());
-    s.tabs_uploaded = true;
+// the one-time uploads of a single-end set: floor tables, read lengths, the per-read output, the reducer
+int single_init_dev(gaml_hip_ctx* c, SingleSet& s) {
+  if (s.tabs_uploaded) return 0;
+  const int lmax = s.mate.max_len;
+  s.floor_tab.resize(lmax + 1); s.logfloor_tab.resize(lmax + 1);
+  for (int v = 0; v <= lmax; v++) {
+    s.floor_tab[v] = std::exp(s.cfg.min_prob_start + s.cfg.min_prob_per_base * v);  // graph.cc:1528
+    s.logfloor_tab[v] = std::log(s.floor_tab[v]);
   }
+  HIP_TRY(c, s.tabs.reserve(2 * (size_t)(lmax + 1) * sizeof(double)));
+  HIP_TRY(c, hipMemcpy(s.tabs.p, s.floor_tab.data(), (lmax + 1) * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(s.tabs.as<double>() + lmax + 1, s.logfloor_tab.data(), (lmax + 1) * sizeof(double), hipMemcpyHostToDevice));
+  const int64_t n = s.mate.n_local();
+  HIP_TRY(c, s.lens.reserve(std::max<size_t>(1, n) * sizeof(int32_t)));
+  if (n) HIP_TRY(c, hipMemcpy(s.lens.p, s.mate.lens.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(c, s.probs.reserve(std::max<size_t>(1, n) * sizeof(double)));
+  HIP_TRY(c, s.red.init());
+  s.tabs_uploaded = true;
+  return 0;
+}
+
+int launch_single(gaml_hip_ctx* c, SingleSet& s, const std::vector<Walk>& paths, int32_t total_len, hipStream_t st, double* out4) {
+  if (int e = single_init_dev(c, s)) return e;
   std::vector<Occ> occs;
   int32_t tl = prepare_single_host(c, s, paths, occs);
   (void)total_len;
@@ -56,6 +62,7 @@ int launch_single(gaml_hip_ctx* c, SingleSet& s, const std::vector<Walk>& paths,
   int slot = stage_acquire(c, s.stage, l0.end, &host);
   if (slot < 0) return slot;
   pack_occ(occ, l0, (char*)host);
+  s.table_bytes = (int64_t)l0.end;
   if (l0.end > s.occ_arena.cap) { HIP_TRY(c, hipStreamSynchronize(st)); HIP_TRY(c, s.occ_arena.reserve(l0.end)); }
   if (int e = stage_upload(c, s.stage, slot, s.occ_arena.p, l0.end, st)) return e;
   if (int e = stage_release(c, s.stage, slot, st)) return e;

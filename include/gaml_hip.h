@@ -301,8 +301,11 @@ int gaml_hip_calc_partials_async(gaml_hip_ctx* ctx, const int32_t* paths, const 
  * A context of paired sets and / or PacBio sets without coverage penalty (BASELINE config 4: paired + PacBio) scores up
  * to 8 path sets per pass over the records instead: per chunk one launch per paired set over its records and one per
  * PacBio set over its cached alignments (occurrence counts of all sets of the chunk side by side per sub-walk), one wait.
- * Same values bit for bit, same gaml_hip_read_probs / gaml_hip_bad_bases / gaml_hip_pacbio_stats afterwards. A single-end
- * set or a PacBio set with a coverage penalty keeps the whole context on the path described above.
+ * Same values bit for bit, same gaml_hip_read_probs / gaml_hip_bad_bases / gaml_hip_pacbio_stats afterwards. A PacBio set
+ * with a coverage penalty keeps the whole context on the path described above. So does a single-end set, unless the
+ * context's switch is on (gaml_hip_set_single_onepass, off by default): then a single-end set goes along as well, one launch
+ * per set and chunk over its read-major records with the occurrence tables of all sets of the chunk side by side
+ * (gaml_hip_single_stats counts the chunks). Same values bit for bit with the switch on or off.
  *   paths / path_offs : all paths of all sets, concatenated (path k = paths[path_offs[k] .. path_offs[k+1]))
  *   set_offs[n_sets+1]: set i = paths set_offs[i] .. set_offs[i+1]-1
  *   probs_out[n_sets]; zeros_out[n_sets * 2 * num_readsets] and total_lens_out[n_sets] may be NULL.
@@ -310,6 +313,13 @@ int gaml_hip_calc_partials_async(gaml_hip_ctx* ctx, const int32_t* paths, const 
  * protocol with one all-reduce over all sets' partials (gaml_amd/dist.py: ShardedScorer.calc_prob_batch). */
 int gaml_hip_calc_prob_batch(gaml_hip_ctx* ctx, int32_t n_sets, const int32_t* paths, const int64_t* path_offs,
                              const int32_t* set_offs, double* probs_out, int32_t* zeros_out, int32_t* total_lens_out);
+/* gaml_hip_set_single_onepass / gaml_hip_get_single_onepass: may single-end sets go along on the one-pass routes of
+ * gaml_hip_calc_prob_batch (1) or does a single-end set keep its context on the sequential path (0, the default). Per
+ * context, any kind of context: in-process multi-device and rank-per-process contexts only keep the flag (their batches
+ * go other ways). A new context starts with 1 when the environment holds GAML_HIP_SINGLE_BATCH=onepass. Same values
+ * either way; the gap-length search of such a context runs on its fallback, whose batches follow the switch. */
+int gaml_hip_set_single_onepass(gaml_hip_ctx* ctx, int32_t on);
+int gaml_hip_get_single_onepass(const gaml_hip_ctx* ctx);
 
 
 /* ---- the advice move of a paired set (ExtendPathsAdv moves.cc:933-998) -------------------------------------------
@@ -413,6 +423,11 @@ int gaml_hip_table_stats(gaml_hip_ctx* ctx, int readset, int64_t* out10);
  * set scored in one multi-set launch}. Host-only contexts too; GAML_HIP_EINVAL for a handle that is not a PacBio set. A
  * multi-device context reports its first shard, like gaml_hip_table_stats. */
 int gaml_hip_pacbio_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
+/* a single-end set: {windows registered, records in the read-major table (those of the windows some scored path set has
+ * named; this shard's reads), bytes of occurrence tables staged by the last call or chunk, gaml_hip_calc_prob_batch chunks
+ * the set scored in one multi-set launch}. Host-only contexts too; GAML_HIP_EINVAL for a handle that is not a single-end
+ * set. A multi-device context reports its first shard, like gaml_hip_pacbio_stats. */
+int gaml_hip_single_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
 /* host-side phase times of the last blocking paired evaluation, microseconds: [0] pass 1 (planner; includes [2]),
  * [1] thresholds + occurrence tables, [2] alignment of newly registered windows (inside pass 1), [3] per-call tables
  * written, [4] record tables / delta lists brought up to date, [5] kernel launches, [6] bytes of per-call tables
