@@ -17,7 +17,9 @@
 //     this file is therefore (a) line-by-line review against the cited reference
 //     lines, (b) the committed golden fixtures under tests/golden produced by THIS
 //     oracle (regression pins, not reference pins), (c) agreement with the
-//     independently structured product host logic + HIP kernels.
+//     independently structured product host logic + HIP kernels, (d) for the paired
+//     term alone: exact arithmetic at 60 digits on hand-made records
+//     (tests/test_crafted_records_host.py; orc_put_window_records files them).
 //
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use it.
 #pragma once

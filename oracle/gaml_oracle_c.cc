@@ -279,6 +279,33 @@ int orc_window_records(void* p, int set, int mate, const int32_t* walk, int n, i
   }
   return cnt;
 }
+// records from outside: the external-aligner branch (graph.cc:924-1033) files what Bowtie2 reported under the sub-walk,
+// ordered by (position, read) (:1024-1026). recs = quadruples (position, edit, read, orientation). Refuses what
+// gaml_hip_put_window_records refuses: -1 bad arguments, -2 a window that is already cached. Returns the records filed.
+int orc_put_window_records(void* p, int set, int mate, const int32_t* walk, int n_walk, const int32_t* recs, int n) {
+  Session* s = S(p);
+  if (!s || set < 0 || set >= (int)s->sets.size() || !walk || n_walk <= 0 || n < 0 || (n > 0 && !recs)) return -1;
+  if (s->sets[set].first == 0 ? mate != 0 : (mate != 0 && mate != 1)) return -1;
+  ShortReadSet* r = short_set(s, set, mate);
+  if (!r) return -1;
+  std::vector<int> key(walk, walk + n_walk);
+  long total = 0;
+  for (int x : key) {
+    if (x < 0 || x >= (int)s->g.seq.size()) return -1;
+    total += s->g.len(x);
+  }
+  if (r->cache.count(key)) return -2;
+  std::vector<Rec> v;
+  for (int i = 0; i < n; i++) {
+    Rec q{recs[4 * i], recs[4 * i + 1], recs[4 * i + 2], recs[4 * i + 3]};
+    if (q.read < 0 || q.read >= r->n() || (q.orient != 0 && q.orient != 1) || q.pos < 0 || q.pos > total) return -1;
+    if (q.edit < 0 || q.edit > 255 || q.edit > r->lens[q.read]) return -1;
+    v.push_back(q);
+  }
+  std::stable_sort(v.begin(), v.end());  // Rec::operator< = (position, read); equal keys keep the caller's order
+  r->cache[key] = v;
+  return n;
+}
 int orc_align_window(void* p, int set, int mate, const int32_t* walk, int n) {
   ShortReadSet* r = short_set(S(p), set, mate);
   std::vector<std::vector<int>> w(1, std::vector<int>(walk, walk + n));

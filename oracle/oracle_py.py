@@ -67,6 +67,7 @@ def _load():
     L.orc_windows_aligned.restype = C.c_long
     L.orc_window_records.argtypes = [C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, _i32p, C.c_int]
     L.orc_align_window.argtypes = [C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int]
+    L.orc_put_window_records.argtypes = [C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, _i32p, C.c_int]
     L.orc_window_keys.argtypes = [C.c_void_p, C.c_int, C.c_int, _i32p, C.c_long]
     L.orc_window_keys.restype = C.c_long
     L.orc_window_string.argtypes = [C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_char_p, C.c_int, _i32p]
@@ -298,6 +299,19 @@ class Oracle:
     def align_window(self, rs, mate, walk):
         walk = np.ascontiguousarray(walk, np.int32)
         return self.L.orc_align_window(self.h, rs, mate, walk, len(walk))
+
+    def put_window_records(self, rs, mate, walk, recs):
+        """File records from outside under cache[walk] (the external-aligner branch, graph.cc:924-1033): recs = rows of
+        (position, edit, read, orientation), ordered here by (position, read) like gaml_hip_put_window_records does. An
+        empty list marks the window as aligned with no hits. Refuses what the library refuses."""
+        walk = np.ascontiguousarray(walk, np.int32)
+        recs = np.ascontiguousarray(recs, np.int32).reshape(-1, 4)
+        n = self.L.orc_put_window_records(self.h, rs, mate, walk, len(walk), recs.reshape(-1) if recs.size else np.zeros(4, np.int32), len(recs))
+        if n == -2:
+            raise RuntimeError("window already cached")
+        if n < 0:
+            raise ValueError("bad arguments")
+        return n
 
     def window_keys(self, rs, mate):
         need = self.L.orc_window_keys(self.h, rs, mate, np.zeros(1, np.int32), 0)
