@@ -331,6 +331,12 @@ def _load():
         L.gaml_hip_single_stats.argtypes = [vp, C.c_int, _i64p]
         L.gaml_hip_set_single_onepass.argtypes = [vp, C.c_int32]
         L.gaml_hip_get_single_onepass.argtypes = [vp]
+    if hasattr(L, "gaml_hip_set_single_device"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_set_single_device.argtypes = [vp, C.c_int32]
+        L.gaml_hip_get_single_device.argtypes = [vp]
+        L.gaml_hip_single_device_stats.argtypes = [vp, C.c_int, _i64p]
+    if hasattr(L, "gaml_hip_debug_single_table_check"):  # development build only
+        L.gaml_hip_debug_single_table_check.argtypes = [vp, C.c_int, _i64p]
     L.gaml_hip_last_phases.argtypes = [vp, _f64p]
     L.gaml_hip_table_stats.argtypes = [vp, C.c_int, _i64p]
     L.gaml_hip_aligner_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -932,6 +938,32 @@ class Context:
         out = np.zeros(4, np.int64)
         self._check(_lib.gaml_hip_single_stats(self._h, rs, out))
         return {"windows": int(out[0]), "records": int(out[1]), "table_bytes": int(out[2]), "multi_launches": int(out[3])}
+
+    def set_single_device(self, on):
+        """Single-end sets: windows aligned on the device in batches, read-major tables built there by kernels
+        (gaml_hip_set_single_device); off by default, or what GAML_HIP_SINGLE_DEVICE=1 set when the context was made."""
+        if not hasattr(_lib, "gaml_hip_set_single_device"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_set_single_device")
+        self._check(_lib.gaml_hip_set_single_device(self._h, 1 if on else 0))
+
+    def get_single_device(self) -> bool:
+        return hasattr(_lib, "gaml_hip_get_single_device") and _lib.gaml_hip_get_single_device(self._h) == 1
+
+    def single_device_stats(self, rs):
+        """{aligned_windows, device_builds, mirrored_records, host_builds} of a single-end set (gaml_hip_single_device_stats):
+        its windows the device aligner took, read-major tables built on the device, records copied into the device's mirror
+        of the record pool, tables built on the host; cumulative."""
+        if not hasattr(_lib, "gaml_hip_single_device_stats"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_single_device_stats")
+        out = np.zeros(4, np.int64)
+        self._check(_lib.gaml_hip_single_device_stats(self._h, rs, out))
+        return {"aligned_windows": int(out[0]), "device_builds": int(out[1]), "mirrored_records": int(out[2]), "host_builds": int(out[3])}
+
+    def debug_single_table_check(self, rs):
+        """The resident read-major table of a single-end set against the host's build, entry by entry (development build)."""
+        out = np.zeros(4, np.int64)
+        self._check(_lib.gaml_hip_debug_single_table_check(self._h, rs, out))
+        return {"compared": int(out[0]), "first": int(out[1]), "extra": int(out[2]), "sizes": int(out[3])}
 
     def aligner_stats(self):
         w, k, us = C.c_int64(), C.c_int64(), C.c_double()

@@ -32,6 +32,7 @@
 #include "paired_multi.hip.h"
 #include "set_kernels.hip.h"
 #include "table_build.hip.h"
+#include "single_tables.hip.h"
 #include "delta_dev.hip.h"
 #include "pacbio_dp.hip.h"
 #include "pacbio_sweep.hip.h"
@@ -411,6 +412,16 @@ struct SgMulti {
   void release() { part_sum.release(); part_zero.release(); ticket.release(); out.release(); }
 };
 
+// a single-end set's side of the device route (gaml_hip_set_single_device; single_tables.hip.h, single_device.hip.h): the
+// host pool's mirror is MateDev::pool / pool_n, the table lands in MateDev::first / extra like the host-built one
+struct SingleTabDev {
+  DevBuf hdr, k_in, k_out, k_tmp, v_in, v_out, v_tmp, hist, flag, before, tiles, zero;  // zero: [0] stays 0 (tb_scan_*'s "entries left out"), [1] the heads of the last build
+  uint64_t built_generation = ~0ull;  // ShortMate::active_generation the DEVICE route built the resident table at (~0: the host route's table, or none)
+  int64_t built_records = 0;          // records of that build
+  int64_t aligned_windows = 0, builds = 0, mirrored = 0, host_builds = 0;  // gaml_hip_single_device_stats
+  void release() { hdr.release(); k_in.release(); k_out.release(); k_tmp.release(); v_in.release(); v_out.release(); v_tmp.release(); hist.release(); flag.release(); before.release(); tiles.release(); zero.release(); }
+};
+
 struct SingleSet {
   gaml_single_cfg cfg;
   ShortMate mate;
@@ -424,6 +435,7 @@ struct SingleSet {
   Staging stage;
   SgMulti multi;
   int64_t table_bytes = 0;  // occurrence tables staged by the last call or chunk (gaml_hip_single_stats)
+  SingleTabDev td;
 };
 
 struct DpDev {  // device buffers of the PacBio banded DP
@@ -508,6 +520,8 @@ struct SetRef { int kind, idx; };
 inline bool gap_penalty_env() { const char* e = getenv("GAML_HIP_GAP_PENALTY"); return e && strcmp(e, "device") == 0; }
 // GAML_HIP_SINGLE_BATCH=onepass: what a new context's single_onepass starts as (read when the context is made)
 inline bool single_onepass_env() { const char* e = getenv("GAML_HIP_SINGLE_BATCH"); return e && strcmp(e, "onepass") == 0; }
+// GAML_HIP_SINGLE_DEVICE=1: what a new context's single_device starts as (read when the context is made)
+inline bool single_device_env() { const char* e = getenv("GAML_HIP_SINGLE_DEVICE"); return e && strcmp(e, "1") == 0; }
 
 }  // namespace detail
 }  // namespace gaml
@@ -567,6 +581,8 @@ struct gaml_hip_ctx {
   int64_t gap_stats[4] = {0, 0, 0, 0};
   bool gap_penalty_device = gap_penalty_env();  // penalised paired sets may take the gap profile's device route (gaml_hip_set_gap_penalty_device)
   bool single_onepass = single_onepass_env();  // single-end sets go along on the batch's one-pass routes (gaml_hip_set_single_onepass)
+  bool single_device = single_device_env();  // single-end sets: windows aligned in device batches, read-major tables built by kernels (gaml_hip_set_single_device)
+  AlnJob single_job;  // a single-end set's pending alignment batch (prepare_single_host): buffers kept from call to call, like aln_job
   std::vector<int32_t> gap_flat;
   std::vector<int64_t> gap_offs;
   // evaluation in progress (between eval_begin and eval_finish)

@@ -12,7 +12,7 @@ int gaml_hip_debug_prepare(gaml_hip_ctx* c, const int32_t* flat, const int64_t* 
   if (!c->have_graph) return fail(c, GAML_HIP_ESTATE, "no graph set");
   std::vector<Walk> paths = unflatten(flat, offs, n_paths);
   for (auto& h : scoring_order(c)) {
-    if (h.kind == 0) { std::vector<Occ> occs; prepare_single_host(c, *c->singles[h.idx], paths, occs); }
+    if (h.kind == 0) { std::vector<Occ> occs; int32_t tl = 0; if (int e = prepare_single_host(c, *c->singles[h.idx], paths, occs, &tl)) return e; }
     else if (h.kind == 1) {
       PairedPrep p;
       PairedSet& ps = *c->paireds[h.idx];
@@ -389,6 +389,35 @@ int gaml_hip_debug_aligner_routes(gaml_hip_ctx* c, int64_t* out4) {
   MULTI_SHARD0(c);
   if (!c || !out4) return fail(c, GAML_HIP_EINVAL, "bad arguments");
   for (int k = 0; k < 4; k++) out4[k] = c->aln_routes[k];
+  return GAML_HIP_OK;
+}
+
+// the resident read-major table of a single-end set against build_read_major, entry by entry; changes no state
+int gaml_hip_debug_single_table_check(gaml_hip_ctx* c, int rs, int64_t* out4) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 0 || !out4) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const SingleSet& s = *c->singles[c->handles[rs].idx];
+  ReadMajor want;
+  build_read_major(s.mate, nullptr, want);
+  out4[0] = (int64_t)(want.first.size() + want.extra.size()); out4[1] = out4[2] = out4[3] = 0;
+  if (c->device < 0) return GAML_HIP_OK;
+  const bool by_device = s.td.built_generation == s.mate.active_generation;
+  if (!by_device && s.dev.uploaded_generation != s.mate.active_generation) return fail(c, GAML_HIP_ESTATE, "the resident table is older than the window cache: score a path set first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int64_t extras = (int64_t)s.rm.extra.size();
+  if (by_device) {
+    int heads = 0;
+    if (s.td.built_records > 0) HIP_TRY(c, hipMemcpy(&heads, s.td.zero.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost));
+    extras = s.td.built_records - heads;
+  }
+  if (extras != (int64_t)want.extra.size()) out4[3]++;
+  if (s.dev.first.cap < want.first.size() * sizeof(RecQuad) || (extras > 0 && s.dev.extra.cap < (size_t)extras * sizeof(RecQuad))) { out4[3]++; return GAML_HIP_OK; }
+  std::vector<RecQuad> first(want.first.size()), extra((size_t)std::max<int64_t>(0, extras));
+  if (!first.empty()) HIP_TRY(c, hipMemcpy(first.data(), s.dev.first.p, first.size() * sizeof(RecQuad), hipMemcpyDeviceToHost));
+  if (!extra.empty()) HIP_TRY(c, hipMemcpy(extra.data(), s.dev.extra.p, extra.size() * sizeof(RecQuad), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < first.size(); i++) out4[1] += memcmp(&first[i], &want.first[i], sizeof(RecQuad)) != 0;
+  for (size_t i = 0; i < std::min(extra.size(), want.extra.size()); i++) out4[2] += memcmp(&extra[i], &want.extra[i], sizeof(RecQuad)) != 0;
   return GAML_HIP_OK;
 }
 

@@ -231,6 +231,7 @@ std::vector<Walk> unflatten(const int32_t* flat, const int64_t* offs, int32_t n)
 
 namespace {
 
+#include "single_device.hip.h"
 #include "single_launch.hip.h"
 #include "single_batch.hip.h"
 #include "pacbio_launch.hip.h"
@@ -508,7 +509,7 @@ void gaml_hip_destroy(gaml_hip_ctx* c) {
     (void)hipDeviceSynchronize();
     if (c->comm) { gaml::comm_destroy(c->comm); c->comm = nullptr; }
     auto drop_stage = [](Staging& s) { for (int k = 0; k < kRing; k++) { s.host[k].release(); if (s.done[k]) (void)hipEventDestroy(s.done[k]); } };
-    for (auto& s : c->singles) { s->dev.first.release(); s->dev.extra.release(); s->dev.pows.release(); s->lens.release(); s->probs.release(); s->tabs.release(); s->occ_arena.release(); s->red.release(); s->multi.release(); drop_stage(s->stage); }
+    for (auto& s : c->singles) { s->dev.first.release(); s->dev.extra.release(); s->dev.pows.release(); s->lens.release(); s->probs.release(); s->tabs.release(); s->occ_arena.release(); s->red.release(); s->multi.release(); s->dev.pool.release(); s->dev.aln.release(); s->td.release(); drop_stage(s->stage); }
     for (auto& s : c->paireds) {
       if (s->rebuild.stream) (void)hipStreamDestroy(s->rebuild.stream);
       if (s->rebuild.done) (void)hipEventDestroy(s->rebuild.done);
@@ -1409,10 +1410,14 @@ int64_t gaml_hip_align_window(gaml_hip_ctx* c, int rs, int mate, const int32_t* 
   MULTI_FWD(c, multi_align_window(c->multi, rs, mate, subpath, len));
   ShortMate* m = mate_of(c, rs, mate);
   if (!m || !subpath || len <= 0 || !c->have_graph) return -2;
+  const SetRef h = c->handles[rs];
+  const bool single_dev = h.kind == 0 && single_device_route(c);  // a single-end set on the device route: the window goes through its batch aligner
+  if (single_dev) m->defer_alignment = true;
   int32_t id = m->align(c->g, Walk(subpath, subpath + len));
+  if (single_dev) m->defer_alignment = false;
   if (m->wins[id].pending) {
-    SetRef h = c->handles[rs];
     if (h.kind == 1) { if (gpu_align_pending(c, *m, c->paireds[h.idx]->dev[mate].aln)) return -3; }
+    else if (single_dev) { if (single_align_pending(c, *c->singles[h.idx])) return -3; }
     else m->flush_pending_cpu(c->g);
   }
   return m->wins[id].count;
@@ -1463,6 +1468,21 @@ int gaml_hip_set_single_onepass(gaml_hip_ctx* c, int32_t on) {
   return GAML_HIP_OK;
 }
 int gaml_hip_get_single_onepass(const gaml_hip_ctx* c) { return c && c->single_onepass ? 1 : 0; }
+
+int gaml_hip_set_single_device(gaml_hip_ctx* c, int32_t on) {
+  if (!c) return GAML_HIP_EINVAL;
+  c->single_device = on != 0;  // (a host-only, multi-device or rank-per-process context only keeps the flag: single_device_route)
+  return GAML_HIP_OK;
+}
+int gaml_hip_get_single_device(const gaml_hip_ctx* c) { return c && c->single_device ? 1 : 0; }
+
+int gaml_hip_single_device_stats(gaml_hip_ctx* c, int rs, int64_t* out4) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 0 || !out4) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const SingleTabDev& T = c->singles[c->handles[rs].idx]->td;
+  out4[0] = T.aligned_windows; out4[1] = T.builds; out4[2] = T.mirrored; out4[3] = T.host_builds;
+  return GAML_HIP_OK;
+}
 
 int gaml_hip_last_phases(gaml_hip_ctx* c, double* out8) {
   if (!c || !out8) return GAML_HIP_EINVAL;

@@ -723,15 +723,16 @@ void occurrences_from_placements(ShortMate& m, const std::vector<Placement>& pl,
 }
 
 void occurrences_single_contig(const GraphStore& g, ShortMate& m, const int32_t* ctg, int32_t n, int32_t st,
-                               int32_t* rank, std::vector<Occ>& out) {
+                               int32_t* rank, std::vector<Occ>& out, int32_t id_limit) {
   // AddPositions (graph.cc:611-647): junction windows only, no position filter; a window missing
-  // from the cache contributes nothing.
+  // from the cache contributes nothing. id_limit: the cache as it stood when it held that many windows (ids are handed
+  // out in registration order) -- a caller that registered later contigs' windows ahead of time looks at the earlier cache.
   int32_t cur_pos = st;
   Walk w;
   for (int32_t i = 0; i < n; i++) {
     junction(g, ctg, n, i, false, w);
     int32_t id = m.find(w);
-    if (id >= 0 && m.wins[id].count > 0) { m.activate(id); out.push_back(Occ{id, cur_pos, INT_MIN / 2, 0, (*rank)++}); }
+    if (id >= 0 && id < id_limit && m.wins[id].count > 0) { m.activate(id); out.push_back(Occ{id, cur_pos, INT_MIN / 2, 0, (*rank)++}); }
     cur_pos += g.len(ctg[i]);
   }
 }

@@ -186,7 +186,7 @@ void placements_paired_contig(const GraphStore& g, const ShortMate& m, const int
 void occurrences_from_placements(ShortMate& m, const std::vector<Placement>& pl, std::vector<Occ>& out);
 // single: contig at absolute coordinate `st` (AddPositions graph.cc:611-647)
 void occurrences_single_contig(const GraphStore& g, ShortMate& m, const int32_t* ctg, int32_t n, int32_t st,
-                               int32_t* rank, std::vector<Occ>& out);
+                               int32_t* rank, std::vector<Occ>& out, int32_t id_limit = INT_MAX);
 
 // read-major record table for the device: every shard read's records in (window id, index in
 // window) order. first[i] holds the read's first record (wid = -1 when it has none) plus the

@@ -44,7 +44,7 @@ int single_chunk_launch(gaml_hip_ctx* c, SgChunk& ch, int n, const int32_t* path
     // must read as absent in the earlier sets' tables, so the tables are built over the final window count
     std::vector<Occ> occs[kMaxSets];
     int32_t tl[kMaxSets];
-    for (int k = 0; k < n; k++) tl[k] = prepare_single_host(c, s, sets[(size_t)k], occs[k]);  // (s.last_occ: the last set's)
+    for (int k = 0; k < n; k++) if (int e = prepare_single_host(c, s, sets[(size_t)k], occs[k], &tl[k])) return e;  // (s.last_occ: the last set's)
     OccTable occ[kMaxSets];
     OccLayout lay[kMaxSets];
     size_t at = 0;
@@ -53,7 +53,7 @@ int single_chunk_launch(gaml_hip_ctx* c, SgChunk& ch, int n, const int32_t* path
       lay[k] = layout_occ(occ[k], at);  // (every offset of a layout is 16-byte aligned)
       at = lay[k].end;
     }
-    if (int e = upload_mate(c, s.mate, s.rm, s.dev, st)) return e;
+    if (int e = single_sync_records(c, s, st)) return e;
     void* host = nullptr;
     const int slot = stage_acquire(c, s.stage, at, &host);
     if (slot < 0) return slot;

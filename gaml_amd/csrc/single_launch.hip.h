@@ -7,24 +7,47 @@
 // single-end read set (CalcScoreForPaths graph.cc:1650-1743)
 // ---------------------------------------------------------------------------------------
 // host: per path (offset by 1,000,000 each, graph.cc:1685), per contig: register + occurrences
-int32_t prepare_single_host(gaml_hip_ctx* c, SingleSet& s, const std::vector<Walk>& paths, std::vector<Occ>& occs) {
+// With the context's switch on (gaml_hip_set_single_device) the loop runs twice: every contig of every path is registered
+// first, its windows deferred; the pending windows are aligned as ONE batch (single_align_pending); then the occurrences are
+// taken in the old order. Registration looks at cache membership alone, never at records, so the window ids come out as they
+// do in one pass. The occurrences of a contig look at the cache as it stood right after that contig's own registration
+// (a window that a LATER contig registers is absent from an earlier one's lookups in one pass: ids are handed out in
+// registration order, so "the cache then" is "ids below the count then"), and with that the occurrences, total_len, rank
+// and the stv offsets are the one-pass ones. Returns 0 or an error; *tl_out = the total length.
+int prepare_single_host(gaml_hip_ctx* c, SingleSet& s, const std::vector<Walk>& paths, std::vector<Occ>& occs, int32_t* tl_out) {
   int32_t rank = 0, tl = 0, stv = 0;
   std::vector<std::pair<int32_t, int32_t>> ranges;
   std::vector<int32_t> gaps;
+  const bool two_pass = single_device_plain(c);
+  std::vector<int32_t> cache_then;  // per contig, in order: the windows cached once it was registered
+  size_t contig = 0;
+  if (two_pass) {
+    s.mate.defer_alignment = true;
+    for (const Walk& path : paths) {
+      split_contigs(path, ranges, gaps);
+      for (size_t ci = 0; ci < ranges.size(); ci++) {
+        register_for_contig(c->g, s.mate, path.data() + ranges[ci].first, ranges[ci].second - ranges[ci].first);
+        cache_then.push_back((int32_t)s.mate.wins.size());
+      }
+    }
+    s.mate.defer_alignment = false;
+    if (int e = single_align_pending(c, s)) return e;
+  }
   for (const Walk& path : paths) {
     split_contigs(path, ranges, gaps);
     for (size_t ci = 0; ci < ranges.size(); ci++) {
       if (ci > 0) tl += gaps[ci - 1];
       const int32_t* ctg = path.data() + ranges[ci].first;
       const int32_t n = ranges[ci].second - ranges[ci].first;
-      register_for_contig(c->g, s.mate, ctg, n);
-      occurrences_single_contig(c->g, s.mate, ctg, n, stv + tl, &rank, occs);
+      if (!two_pass) register_for_contig(c->g, s.mate, ctg, n);
+      occurrences_single_contig(c->g, s.mate, ctg, n, stv + tl, &rank, occs, two_pass ? cache_then[contig++] : INT_MAX);
       for (int32_t k = 0; k < n; k++) tl += c->g.len(ctg[k]);
     }
     stv += 1000000;
   }
   s.last_occ = occs;
-  return tl;
+  *tl_out = tl;
+  return 0;
 }
 
 // the one-time uploads of a single-end set: floor tables, read lengths, the per-read output, the reducer
@@ -51,12 +74,13 @@ int single_init_dev(gaml_hip_ctx* c, SingleSet& s) {
 int launch_single(gaml_hip_ctx* c, SingleSet& s, const std::vector<Walk>& paths, int32_t total_len, hipStream_t st, double* out4) {
   if (int e = single_init_dev(c, s)) return e;
   std::vector<Occ> occs;
-  int32_t tl = prepare_single_host(c, s, paths, occs);
+  int32_t tl = 0;
+  if (int e = prepare_single_host(c, s, paths, occs, &tl)) return e;
   (void)total_len;
   OccTable occ;
   build_occ_table(s.mate.wins.size(), occs, occ);
   const double t_after_host = now_us();
-  if (int e = upload_mate(c, s.mate, s.rm, s.dev, st)) return e;
+  if (int e = single_sync_records(c, s, st)) return e;
   OccLayout l0 = layout_occ(occ, 0);
   void* host = nullptr;
   int slot = stage_acquire(c, s.stage, l0.end, &host);

@@ -320,6 +320,15 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* ctx, int32_t n_sets, const int32_t* p
  * either way; the gap-length search of such a context runs on its fallback, whose batches follow the switch. */
 int gaml_hip_set_single_onepass(gaml_hip_ctx* ctx, int32_t on);
 int gaml_hip_get_single_onepass(const gaml_hip_ctx* ctx);
+/* gaml_hip_set_single_device / gaml_hip_get_single_device: are the windows of single-end sets aligned on the device, one
+ * batch per path set that brings new ones, and their read-major record tables built there by kernels from a mirror of the
+ * host's record pool (1), or does the host align window by window and build and upload the whole table whenever a window
+ * joins (0, the default). Per context, settable at any time, effective from the next evaluation; the table is rebuilt on
+ * the other route after a flip. Served on plain single-device contexts: host-only, in-process multi-device and
+ * rank-per-process contexts only keep the flag and stay on the host route. A new context starts with 1 when the
+ * environment holds GAML_HIP_SINGLE_DEVICE=1. Same records, same tables, same values bit for bit either way. */
+int gaml_hip_set_single_device(gaml_hip_ctx* ctx, int32_t on);
+int gaml_hip_get_single_device(const gaml_hip_ctx* ctx);
 
 
 /* ---- the advice move of a paired set (ExtendPathsAdv moves.cc:933-998) -------------------------------------------
@@ -401,7 +410,9 @@ int64_t gaml_hip_align_window(gaml_hip_ctx* ctx, int readset, int mate, const in
 /* GPU window aligner (cold path): windows aligned on the device so far, seed candidates extended, wall time.
  * The device aligns the windows of a paired set's mate whose reads have at most 510 bases and whose indexed read
  * length is at least 16; every other mate, single-end sets and host-only contexts are served by the library's host
- * aligner with identical records, and do not count here -- counters that stay at zero mean the host aligner ran.
+ * aligner with identical records, and do not count here -- counters that stay at zero mean the host aligner ran. A
+ * single-end set whose reads fit the same bounds counts here as well when its context's switch is on
+ * (gaml_hip_set_single_device): its windows then go to the device in batches.
  * (Development builds: GAML_HIP_KNOB_ALIGNER_ROUTE = GAML_HIP_ALIGNER_HOST, gaml_hip_debug.h, forces the host aligner.) */
 int gaml_hip_aligner_stats(gaml_hip_ctx* ctx, int64_t* windows, int64_t* candidates, double* microseconds);
 /* the same time by stage, host clock, cumulative: out6 = {window strings + upload, spans + candidates (small batches: the
@@ -428,6 +439,11 @@ int gaml_hip_pacbio_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
  * the set scored in one multi-set launch}. Host-only contexts too; GAML_HIP_EINVAL for a handle that is not a single-end
  * set. A multi-device context reports its first shard, like gaml_hip_pacbio_stats. */
 int gaml_hip_single_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
+/* the device route of a single-end set (gaml_hip_set_single_device): {windows of this set aligned by the device aligner,
+ * read-major tables built on the device, records copied into the device's mirror of the record pool, tables built on the
+ * host (the route of a context whose switch is off)}, all cumulative. Host-only contexts too (the first three stay 0);
+ * GAML_HIP_EINVAL for a handle that is not a single-end set. A multi-device context reports its first shard. */
+int gaml_hip_single_device_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
 /* host-side phase times of the last blocking paired evaluation, microseconds: [0] pass 1 (planner; includes [2]),
  * [1] thresholds + occurrence tables, [2] alignment of newly registered windows (inside pass 1), [3] per-call tables
  * written, [4] record tables / delta lists brought up to date, [5] kernel launches, [6] bytes of per-call tables

@@ -176,6 +176,13 @@ int gaml_hip_debug_occ_check(gaml_hip_ctx* ctx, int readset, int64_t* out4);
  * candidates, pool full), batches flushed to the host aligner after the sixth attempt}. */
 int gaml_hip_debug_aligner_routes(gaml_hip_ctx* ctx, int64_t* out4);
 
+/* The resident read-major table of single-end set `readset` against the host's build_read_major over the window cache as
+ * it stands, entry by entry, whichever route built it (gaml_hip_set_single_device): waits for the library's stream, copies
+ * first[] / extra[] back, changes no state. out4 = {entries compared (reads + further records), mismatching first[]
+ * entries, mismatching extra[] entries, sizes that differ}. A host-only context reports the sizes and zeros. GAML_HIP_ESTATE
+ * when windows were activated since the last scoring call (the table is older than the cache). */
+int gaml_hip_debug_single_table_check(gaml_hip_ctx* ctx, int readset, int64_t* out4);
+
 /* bad_bases of paired set `readset` for every path set of the last gaml_hip_calc_prob_batch, in the batch's order, whichever
  * route its chunks took (0 for a set without coverage penalty). Returns the number of path sets; at most `cap` are written.
  * A batch over penalised sets: GAML_HIP_KNOB_BATCH_ROUTE at 0 takes the one-pass routes (tables from patches, else whole; the
