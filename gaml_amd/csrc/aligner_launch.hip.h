@@ -84,12 +84,10 @@ int aln_small_reserve(gaml_hip_ctx* c, AlignSmall& S) {
   HIP_TRY(c, S.hits.reserve((size_t)kFastCands * sizeof(AlnHit)));
   HIP_TRY(c, S.wcopy.reserve(((size_t)1 << 18) + 64));  // a batch's window strings in ordinary device memory (span_cands_kernel writes, extend_pair2_kernel reads)
   if (!S.out_host.p) { HIP_TRY(c, S.out_host.reserve(64 + 64 + (size_t)kFastCands * sizeof(AlnHit))); memset(S.out_host.p, 0, 128); }
-  if (!S.in_dev) {
+  if (!S.in.dev) {
     const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
-    const size_t want = (size_t)1 << 18;
-    if (direct) HIP_TRY(c, hipExtMallocWithFlags(&S.in_dev, want, hipDeviceMallocFinegrained));
-    else { HIP_TRY(c, hipMalloc(&S.in_dev, want)); HIP_TRY(c, S.in_host.reserve(want)); }
-    S.in_cap = want; S.in_direct = direct;
+    HIP_TRY(c, S.in.alloc((size_t)1 << 18, direct));
+    if (!direct) HIP_TRY(c, S.in.host.reserve((size_t)1 << 18));
   }
   return 0;
 }
@@ -126,23 +124,16 @@ int aln_small_enqueue(gaml_hip_ctx* c, const ShortMate& m, AlignDev& d, AlignSma
   if (nw == 0 || nw > 4096 || in_bytes > ((size_t)1 << 20) || job.blk[(size_t)nw] == 0) return 1;
   // input block: [windows][code-buffer offsets][window strings]
   const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
-  if (in_bytes > S.in_cap || S.in_direct != direct) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (S.in_dev) { HIP_TRY(c, hipFree(S.in_dev)); S.in_dev = nullptr; }
-    const size_t want = std::max<size_t>(in_bytes * 2, (size_t)1 << 16);
-    if (direct) HIP_TRY(c, hipExtMallocWithFlags(&S.in_dev, want, hipDeviceMallocFinegrained));
-    else HIP_TRY(c, hipMalloc(&S.in_dev, want));
-    S.in_cap = want; S.in_direct = direct;
-  }
-  char* wp = (char*)S.in_dev;
-  if (!direct) { HIP_TRY(c, S.in_host.reserve(in_bytes)); wp = (char*)S.in_host.p; }
+  if (in_bytes > S.in.cap || S.in.direct != direct) HIP_TRY(c, S.in.reserve(std::max<size_t>(in_bytes * 2, (size_t)1 << 16), direct, st));
+  char* wp = (char*)S.in.dev;
+  if (!direct) { HIP_TRY(c, S.in.host.reserve(in_bytes)); wp = (char*)S.in.host.p; }
   const size_t off_blk = align16(nw * sizeof(AlnWindow)), off_str = off_blk + align16((nw + 1) * sizeof(int32_t));
   memcpy(wp, job.wins.data(), nw * sizeof(AlnWindow));
   memcpy(wp + off_blk, job.blk.data(), (nw + 1) * sizeof(int32_t));
   memcpy(wp + off_str, job.wstr.data(), job.wstr.size());
   if (direct) _mm_sfence();
-  else HIP_TRY(c, hipMemcpyAsync(S.in_dev, S.in_host.p, in_bytes, hipMemcpyHostToDevice, st));
-  const char* dbase = (const char*)S.in_dev;
+  else HIP_TRY(c, hipMemcpyAsync(S.in.dev, S.in.host.p, in_bytes, hipMemcpyHostToDevice, st));
+  const char* dbase = (const char*)S.in.dev;
   if (int e = aln_small_reserve(c, S)) return e;
   const AlnWindow* d_wins = (const AlnWindow*)dbase;
   const int* d_blk = (const int*)(dbase + off_blk);
@@ -187,8 +178,8 @@ int aln_small_collect(gaml_hip_ctx* c, AlignSmall& S, AlnJob& job, std::vector<A
 #endif
 #ifdef GAML_HIP_DEV
   static const int keepalive = getenv("GAML_ALN_KEEPALIVE") ? atoi(getenv("GAML_ALN_KEEPALIVE")) : 0;  // A/B: PCIe traffic from the host while it waits: 1 reads through the BAR, 2 writes
-  if (keepalive && S.in_direct && S.in_dev) {
-    volatile unsigned* bar = (volatile unsigned*)((char*)S.in_dev + S.in_cap - 64);  // (the input block's last line: no batch reaches it)
+  if (keepalive && S.in.direct && S.in.dev) {
+    volatile unsigned* bar = (volatile unsigned*)((char*)S.in.dev + S.in.cap - 64);  // (the input block's last line: no batch reaches it)
     unsigned sink = 0, tick = 0;
     while (!seen && now_us() - t0 < 5000.0) {
       for (int k = 0; k < 64 && !seen; k++) { if (keepalive == 1) sink += *bar; else { *bar = ++tick; _mm_sfence(); } seen = *word == job.seq; }
@@ -198,8 +189,8 @@ int aln_small_collect(gaml_hip_ctx* c, AlignSmall& S, AlnJob& job, std::vector<A
   if (wait_mode == 5) {  // A/B: spin on the (cached) word without PAUSE -- a virtual CPU that executes PAUSE in a loop may be descheduled by its hypervisor
     while (!seen && now_us() - t0 < 5000.0) { for (int k = 0; k < 4096 && !seen; k++) seen = *word == job.seq; }
   }
-  if ((wait_mode == 3 || wait_mode == 4) && S.in_direct && S.in_dev) {  // A/B: a read through the BAR per poll keeps the PCIe link out of its idle states
-    volatile unsigned* bar = (volatile unsigned*)S.in_dev;
+  if ((wait_mode == 3 || wait_mode == 4) && S.in.direct && S.in.dev) {  // A/B: a read through the BAR per poll keeps the PCIe link out of its idle states
+    volatile unsigned* bar = (volatile unsigned*)S.in.dev;
     unsigned sink = 0;
     while (!seen && now_us() - t0 < 5000.0) { for (int k = 0; k < 64 && !seen; k++) { sink += *bar; seen = *word == job.seq; } }
     if (sink == 0x12345678u) fprintf(stderr, "\n");
@@ -369,21 +360,21 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
   if (nw > 4096 || in_bytes > ((size_t)1 << 18) || job.blk[(size_t)nw] == 0) return 1;
   if (int e = aln_small_reserve(c, S)) return e;
   const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
-  if (in_bytes > S.in_cap || S.in_direct != direct) return 1;  // (the per-mate route sizes its own input block)
+  if (in_bytes > S.in.cap || S.in.direct != direct) return 1;  // (the per-mate route sizes its own input block)
   // a handful of windows and their strings travel with the launches themselves (AlnWinArgs, AlnStrArgs); otherwise
   // through the input block: [windows][code-buffer offsets][window strings]
   const bool in_args = nw <= kAlnArgWins && job.wstr.size() <= (size_t)kAlnArgStr && KNOB(c, ALIGNER_ROUTE) != GAML_HIP_ALIGNER_INPUT_BLOCK;  // INPUT_BLOCK: always the input block (tests)
   const size_t off_blk = align16(nw * sizeof(AlnWindow)), off_str = off_blk + align16((nw + 1) * sizeof(int32_t));
   if (!in_args) {
-    char* wp = (char*)S.in_dev;
-    if (!direct) { HIP_TRY(c, S.in_host.reserve(in_bytes)); wp = (char*)S.in_host.p; }
+    char* wp = (char*)S.in.dev;
+    if (!direct) { HIP_TRY(c, S.in.host.reserve(in_bytes)); wp = (char*)S.in.host.p; }
     memcpy(wp, job.wins.data(), nw * sizeof(AlnWindow));
     memcpy(wp + off_blk, job.blk.data(), (nw + 1) * sizeof(int32_t));
     memcpy(wp + off_str, job.wstr.data(), job.wstr.size());
     if (direct) _mm_sfence();
-    else HIP_TRY(c, hipMemcpyAsync(S.in_dev, S.in_host.p, in_bytes, hipMemcpyHostToDevice, st));
+    else HIP_TRY(c, hipMemcpyAsync(S.in.dev, S.in.host.p, in_bytes, hipMemcpyHostToDevice, st));
   }
-  const char* dbase = (const char*)S.in_dev;
+  const char* dbase = (const char*)S.in.dev;
   const AlnWindow* d_wins = (const AlnWindow*)dbase;
   const int* d_blk = (const int*)(dbase + off_blk);
   const char* d_wstr = dbase + off_str;
@@ -429,8 +420,8 @@ int aln_pair_small(gaml_hip_ctx* c, PairedSet& ps) {
 #ifdef GAML_HIP_DEV
   // A/B (GAML_ALN_WAIT=2): events attached to the two dispatches -- the device's own begin / end stamps next to the host's wait
   static const int ev_mode = getenv("GAML_ALN_WAIT") ? atoi(getenv("GAML_ALN_WAIT")) : 0;
-  hipEvent_t* const aev = S.probe_ev;  // (per context: events belong to the device and thread that made them)
-  if ((ev_mode == 2 || ev_mode == 4 || ev_mode == 6) && !aev[0]) for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventCreate(&aev[k]));
+  Event* const aev = S.probe_ev;  // (per context: events belong to the device and thread that made them)
+  if (ev_mode == 2 || ev_mode == 4 || ev_mode == 6) for (int k = 0; k < 4; k++) HIP_TRY(c, aev[k].ensure(hipEventDefault));
   const bool timed = ev_mode == 2 || ev_mode == 4 || ev_mode == 6;
 #else
   constexpr bool timed = false;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include "resource.hip.h"
 #include "radix_sort.hip.h"
 
 #include <algorithm>
@@ -79,69 +80,6 @@ inline void gpu_probe(hipStream_t st, void* p4, const char* label) {
 #endif
 }
 
-// grow-only device / pinned buffers
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-    size_t want = std::max(bytes + bytes / 4, (size_t)256);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T* as() const { return (T*)p; }
-};
-struct PinBuf {
-  void* p = nullptr;
-  void* dev = nullptr;  // the same memory as the device sees it
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) { (void)hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
-    size_t want = std::max(bytes + bytes / 4, (size_t)4096);
-    // device-visible (kernels read / write it directly) and coherent: the host polls words the device writes (per-block
-    // partials, sequence words) without any runtime call in between
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&dev, p, 0);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
-};
-
-constexpr int kRing = 4;  // staging slots, so that async callers may run ahead of the device
-
-struct Staging {
-  PinBuf host[kRing];
-  hipEvent_t done[kRing] = {};
-  bool armed[kRing] = {};
-  int next = 0;
-};
-
-// Per-call tables of a paired set: a ring of device slots. On a large-BAR device the host writes a slot directly
-// (fine-grained device memory behind the PCIe BAR); otherwise through the pinned twin + a copy (paired_launch.hip.h).
-struct Arena {
-  void* dev[kRing] = {};
-  size_t cap[kRing] = {};
-  bool direct[kRing] = {};
-  PinBuf host[kRing];
-  hipEvent_t done[kRing] = {};
-  bool armed[kRing] = {};
-  int next = 0;
-  void release() {
-    for (int k = 0; k < kRing; k++) {
-      if (dev[k]) (void)hipFree(dev[k]);
-      dev[k] = nullptr; cap[k] = 0;
-      host[k].release();
-      if (done[k]) (void)hipEventDestroy(done[k]);
-      done[k] = nullptr; armed[k] = false;
-    }
-  }
-};
-
 struct Reducer {  // per read set: partials + ticket + 2-double result
   DevBuf part_sum, part_zero, ticket, out;
   hipError_t init() {
@@ -154,7 +92,6 @@ struct Reducer {  // per read set: partials + ticket + 2-double result
     if ((e = hipMemset(out.p, 0, 4 * sizeof(double))) != hipSuccess) return e;
     return hipDeviceSynchronize();  // the scoring stream is non-blocking: make the zeroes land first
   }
-  void release() { part_sum.release(); part_zero.release(); ticket.release(); out.release(); }
 };
 
 struct AlignDev {  // device copies the GPU aligner needs: reads (1 byte per base) + the max-hash index
@@ -162,7 +99,6 @@ struct AlignDev {  // device copies the GPU aligner needs: reads (1 byte per bas
   DevBuf htab;     // key -> bucket, open addressing (AlnHashSlot, 2^hbits slots; hbits = 0: none)
   int hbits = 0;
   bool uploaded = false;
-  void release() { reads.release(); read_off.release(); bucket_hash.release(); bucket_top.release(); bucket_off.release(); bucket_reads.release(); htab.release(); }
 };
 struct AlignScratch {  // per context, grown on demand
   DevBuf wstr, wins, blk, spans, cands, hits, counters;
@@ -171,8 +107,6 @@ struct AlignScratch {  // per context, grown on demand
   // job's vectors made the runtime register those pages with the device -- and FREEING such a buffer afterwards makes the
   // driver evict the process's queues: the first dispatch after the cold batch started 12-25 ms late, the device idle.)
   PinBuf stage;
-  void release() { wstr.release(); wins.release(); blk.release(); spans.release(); cands.release(); hits.release(); counters.release();
-                   sort_keys.release(); sort_idx.release(); sort_tmp.release(); hits_sorted.release(); file_tmp.release(); stage.release(); }
 };
 
 // small batches (aln_small_*): one set of buffers per mate, so that the two mates' pipelines run side by side. Input
@@ -180,18 +114,12 @@ struct AlignScratch {  // per context, grown on demand
 // pinned memory behind a sequence word.
 struct AlignSmall {
   DevBuf spans, cands, hits, counters, wcopy;
-  void* in_dev = nullptr; size_t in_cap = 0; bool in_direct = false;
-  PinBuf in_host, out_host;
+  HostBlock in;     // [windows][code-buffer offsets][window strings] of a batch
+  PinBuf out_host;
   AlnStrArgs str_args;  // a small batch's window strings as they travel in the launches' argument segments
   unsigned long long out_seq = 0;
   double seen_us = 0;   // host clock when the last batch's sequence word was seen (timing builds)
-  hipEvent_t probe_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // timing probes of the development build (GAML_ALN_WAIT)
-  void release() {
-    spans.release(); cands.release(); hits.release(); counters.release(); wcopy.release();
-    for (int k = 0; k < 4; k++) if (probe_ev[k]) { (void)hipEventDestroy(probe_ev[k]); probe_ev[k] = nullptr; }
-    if (in_dev) (void)hipFree(in_dev);
-    in_dev = nullptr; in_cap = 0; in_host.release(); out_host.release();
-  }
+  Event probe_ev[4];  // timing probes of the development build (GAML_ALN_WAIT)
 };
 // one batch of pending windows of one mate: strings built once, possibly already in flight on the device
 struct AlnJob {
@@ -232,21 +160,12 @@ struct TableDev {
 #endif
   std::vector<int32_t> read_of_slot_host;  // fetched on demand (gaml_hip_read_probs)
   bool ros_valid = false;
-  void release() {
-    for (int m = 0; m < 2; m++) { rec8[m].release(); first[m].release(); extra[m].release(); inl[m].release(); }
-    len_code.release(); len12.release(); static_idx.release(); static_val.release(); slot_of_read.release(); read_of_slot.release(); dirty_of_slot.release(); cnt.release();
-  }
 };
 
 // scratch of a table build (one build at a time per set)
 struct BuildScratch {
   DevBuf k_in, k_out, k_tmp, v_in, v_tmp, hist, v_sorted[2], rstart[2], rend[2], one[2], cl, sidx, more[2], start[2], tiles, wins[2], peer0;
   PinBuf h_wins[2], h_peer, h_cnt;
-  void release() {
-    k_in.release(); k_out.release(); k_tmp.release(); v_in.release(); v_tmp.release(); hist.release(); cl.release(); sidx.release(); tiles.release(); peer0.release();
-    for (int m = 0; m < 2; m++) { v_sorted[m].release(); rstart[m].release(); rend[m].release(); one[m].release(); more[m].release(); start[m].release(); wins[m].release(); h_wins[m].release(); }
-    h_peer.release(); h_cnt.release();
-  }
 };
 
 // A rebuild of the record tables beside the evaluations: the build is a chain of kernels on a stream of its own over the
@@ -263,12 +182,14 @@ struct TableRebuild {
   int next_slice = 0;          // slices of the build's launch chain enqueued so far
   int64_t start_eval = 0;      // the set's evaluation count when the rebuild was decided
   TableDev tab;                // the spare set of buffers: being built, or idle
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr, mark = nullptr;
+  Stream stream;
+  Event done, mark;
   std::vector<std::pair<int32_t, int32_t>> after;  // (mate, window) activated since the build started: not in the new tables
 };
 
 // what the host keeps of the live tables (the tables themselves exist on the device only)
+using EventPair = std::pair<Event, Event>;  // around a scoring launch (gaml_hip_set_event_timing)
+
 struct PairInfo {
   int64_t class_count[4] = {0, 0, 0, 0};  // 0: compact; 1: <= 2 records; 2: <= 4; 3: more
   int64_t n0a = 0;                        // static part of the compact class
@@ -291,10 +212,6 @@ struct AdviceDev {
   uint32_t serial = 0;
   std::vector<AdviceStep> steps;        // the last query's walk ...
   std::vector<int32_t> list;            // ... and its candidates
-  void release() {
-    offs.release(); ent.release(); scratch.release(); first.release(); last.release(); cnt.release(); at.release(); tiles.release();
-    in.release(); mask.release(); out.release(); h_in.release(); h_out.release();
-  }
 };
 
 struct PairedSet {
@@ -351,13 +268,12 @@ struct PairedSet {
   // of the previous call is done when the call returns): a call that shares most paths with the previous one writes
   // a few dozen 12-byte entries through the BAR instead of the whole image. Capacities leave room to grow.
   struct Persist {
-    void* dev = nullptr; size_t bytes = 0;
+    HostBlock blk;                     // (always fine-grained memory: the route exists on a large-BAR device only; blk.cap: bytes of the layout)
     size_t cap_w[2] = {0, 0}, cap_lo[2] = {0, 0}, cap_m[2] = {0, 0};  // table entries / list bounds / list entries per mate
     size_t off_tfloor = 0, off_occ[2] = {0, 0}, off_lo[2] = {0, 0}, off_m[2] = {0, 0};
     size_t cap_cov = 0, off_cov = 0;   // coverage layout of the call (penalty_constant > 0): int32 entries / where they start; written whole per call
     bool valid = false;                // the copy mirrors the host images as of their last take_changed()
     size_t last_bytes = 0;             // table entries + coverage layout the last update wrote (gaml_hip_last_phases()[6])
-    void release() { if (dev) (void)hipFree(dev); dev = nullptr; bytes = 0; valid = false; }
   } persist;
   // Whole-set blocking calls on the resident route build the occurrence tables on the device (occ_device.hip.h): every
   // memo's prepacked entries (PathMemo::pre) stay in a pool in device memory, a call sends one descriptor per path and
@@ -381,17 +297,9 @@ struct PairedSet {
     size_t shared_next = 0;
     std::vector<uint64_t> key;         // this call's combination
     int64_t dev_calls = 0, host_calls = 0, fallbacks = 0, compactions = 0;
-    void release() {
-      for (int mt = 0; mt < 2; mt++) {
-        pool[mt].release(); stamp[mt].release();
-        for (int k = 0; k < 2; k++) { tab[mt][k].release(); list[mt][k].release(); }
-      }
-      stage.release(); dup.release();
-    }
   } occdev;
   int64_t batches_patched = 0, batches_full = 0;  // gaml_hip_calc_prob_batch chunks whose per-set tables were built on the device from patches / written whole
   size_t batch_slack = 0;             // extra bytes per path set region of a batch (grows when a set's tables did not fit)
-  hipEvent_t ev_tables = nullptr, ev_ovf = nullptr;
   PairedPlanner planner;
   OccImage image[2];                 // persistent host images of the occurrence tables, patched per call
   std::vector<Occ> scratch_occ[2];   // debug dumps only
@@ -409,7 +317,6 @@ struct SgMulti {
   DevBuf part_sum, part_zero, ticket;  // per set and block; a ticket of its own (single_score_multi_kernel)
   PinBuf out;       // {sum, floored, 0, reads} per set, written by the last block
   int64_t launches = 0;
-  void release() { part_sum.release(); part_zero.release(); ticket.release(); out.release(); }
 };
 
 // a single-end set's side of the device route (gaml_hip_set_single_device; single_tables.hip.h, single_device.hip.h): the
@@ -419,7 +326,6 @@ struct SingleTabDev {
   uint64_t built_generation = ~0ull;  // ShortMate::active_generation the DEVICE route built the resident table at (~0: the host route's table, or none)
   int64_t built_records = 0;          // records of that build
   int64_t aligned_windows = 0, builds = 0, mirrored = 0, host_builds = 0;  // gaml_hip_single_device_stats
-  void release() { hdr.release(); k_in.release(); k_out.release(); k_tmp.release(); v_in.release(); v_out.release(); v_tmp.release(); hist.release(); flag.release(); before.release(); tiles.release(); zero.release(); }
 };
 
 struct SingleSet {
@@ -440,7 +346,6 @@ struct SingleSet {
 
 struct DpDev {  // device buffers of the PacBio banded DP
   DevBuf path, jobs, ops, scratch, out, dbg;
-  void release() { path.release(); jobs.release(); ops.release(); scratch.release(); out.release(); dbg.release(); }
 };
 
 // coverage sweep of a PacBio set with a penalty (pacbio_sweep.hip.h)
@@ -454,11 +359,6 @@ struct PbSweepDev {
   DevBuf in, all;
   DevBuf key_begin, key_end, pos, key_begin_s, key_end_s, pos_s, end_max, tmp, bad;
   Staging stage;
-  void release() {
-    iv_off.release(); iv.release(); in.release(); all.release(); key_begin.release(); key_end.release(); pos.release();
-    key_begin_s.release(); key_end_s.release(); pos_s.release(); end_max.release(); tmp.release(); bad.release();
-    for (int k = 0; k < kRing; k++) { stage.host[k].release(); if (stage.done[k]) (void)hipEventDestroy(stage.done[k]); stage.done[k] = nullptr; stage.armed[k] = false; }
-  }
 };
 
 // what a path contributes to a PacBio evaluation (pacbio_enumerate): its cached sub-walks in the order the reference
@@ -474,7 +374,6 @@ struct PbMulti {
   DevBuf part_sum, part_zero, ticket;  // per set and block; a ticket of its own (pacbio_score_multi_kernel)
   PinBuf out;       // {sum, floored, 0, reads} per set, written by the last block
   int64_t launches = 0;
-  void release() { count.release(); part_sum.release(); part_zero.release(); ticket.release(); out.release(); }
 };
 
 struct PacbioSet {
@@ -530,13 +429,14 @@ using namespace gaml;          // (this header is private to the library's two H
 using namespace gaml::detail;
 
 struct gaml_hip_ctx {
+  // (first, so that they go last: everything below that was used on them is destroyed while they exist)
+  Stream stream;
+  Stream aux_stream;  // the overflow kernel runs beside the main kernel
   gaml::MultiState* multi = nullptr;  // several device shards behind this context (gaml_hip_create_multi): every call is forwarded
   gaml::CommState* comm = nullptr;    // RCCL communicator of a sharded context (gaml_hip_comm_init_rank / the shards of a multi context)
   int device = -1;
   DevBuf warm_buf; bool general_warm = false;  // warm_general_kernels (gaml_hip.hip)
   AlnJob aln_job[2];  // the two mates' pending alignment batches (align_pending_pair): buffers kept from call to call
-  hipStream_t stream = nullptr;
-  hipStream_t aux_stream = nullptr;  // the overflow kernel runs beside the main kernel
   GraphStore g;
   bool have_graph = false;
   std::vector<std::unique_ptr<SingleSet>> singles;
@@ -560,7 +460,7 @@ struct gaml_hip_ctx {
   bool event_timing = false;
   int event_every = 1;    // time every k-th scoring launch (attached events cost ~4 us of host time per launch)
   int64_t event_tick = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;  // one pair per scoring launch of a call
+  std::vector<EventPair> ev_pool;  // one pair per scoring launch of a call
   std::vector<uint64_t> ev_call;  // ... and the evaluation (eval_serial) it belongs to
   uint64_t eval_serial = 0;
   size_t ev_used = 0;
@@ -573,7 +473,7 @@ struct gaml_hip_ctx {
   char* shm_base = nullptr; size_t shm_bytes = 0; int shm_rank = 0, shm_world = 0, shm_cap = 0; unsigned long long shm_step = 0; std::string shm_name;
   PinBuf fetch_host;            // gaml_hip_fetch_async / _wait: [sequence word | 63 x pad | doubles]
   unsigned long long fetch_seq = 0;
-  hipStream_t fetch_stream = nullptr;
+  hipStream_t fetch_stream = nullptr;  // where the last fetch went: the caller's stream or this context's, not owned
   DevBuf batch_dev;  // gaml_hip_calc_prob_batch: 4 doubles per read set and path set
   PinBuf batch_host;
   // gaml_hip_gap_profile / gaml_hip_fix_gap_length (gap_profile.hip.h): {profile calls, lengths scored on the device route, on the

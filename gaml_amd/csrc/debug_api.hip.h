@@ -90,9 +90,9 @@ int32_t gaml_hip_debug_gap_cov_layout(gaml_hip_ctx* c, int rs, int g, int32_t* s
   if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 1 || c->device < 0) return -1;
   PairedSet& ps = *c->paireds[c->handles[rs].idx];
   const PairedSet::GapCov& G = ps.gap_cov;
-  if (G.slot < 0 || g < 0 || g >= G.n || !ps.arena.dev[G.slot]) return -1;  // no device gap pass of a penalised set yet, or no such region
+  if (G.slot < 0 || g < 0 || g >= G.n || !ps.arena.slot[G.slot].dev) return -1;  // no device gap pass of a penalised set yet, or no such region
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-  const char* region = (const char*)ps.arena.dev[G.slot] + (size_t)g * G.stride;
+  const char* region = (const char*)ps.arena.slot[G.slot].dev + (size_t)g * G.stride;
   std::vector<int32_t> sb((size_t)G.n_sb), pb((size_t)G.n_pb), so((size_t)G.n_pb), stv((size_t)std::max(1, G.n_st));
   if (hipMemcpy(sb.data(), region + G.sb_off, sb.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   if (hipMemcpy(pb.data(), region + G.pb_off, pb.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
@@ -225,7 +225,6 @@ int gaml_hip_debug_radix_sort(gaml_hip_ctx* c, uint64_t* keys, uint64_t* vals, i
   if (vals) HIP_TRY(c, hipMemcpyAsync(vals, v_out.p, bytes, hipMemcpyDeviceToHost, st));
   if (run_max) HIP_TRY(c, hipMemcpyAsync(run_max, mx.p, bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  for (DevBuf* b : {&k_in, &k_out, &k_tmp, &v_in, &v_out, &v_tmp, &hist, &rm, &mx}) b->release();
   return 0;
 }
 
@@ -320,7 +319,7 @@ int gaml_hip_debug_tables_check(gaml_hip_ctx* c, int rs, int64_t* out8) {
   TableDev T;
   if (int e = paired_build_enqueue(c, s, T, c->stream)) return e;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (int e = paired_build_collect(c, s, T)) { T.release(); return e; }
+  if (int e = paired_build_collect(c, s, T)) return e;
   // host side
   ShortMate hm[2];
   for (int mt = 0; mt < 2; mt++) {
@@ -372,7 +371,6 @@ int gaml_hip_debug_tables_check(gaml_hip_ctx* c, int rs, int64_t* out8) {
   }
   out8[0] = n; out8[1] = T.class_count[0]; out8[2] = T.n0a; out8[3] = T.class_count[1]; out8[4] = T.class_count[2]; out8[5] = T.class_count[3];
   out8[6] = compared; out8[7] = bad;
-  T.release();
   return bad ? fail(c, GAML_HIP_ESTATE, "record tables: the device build differs from the host restatement") : GAML_HIP_OK;
 }
 

@@ -82,19 +82,16 @@ struct CrashHook {
 #endif  // GAML_HIP_DEV
 
 int stage_acquire(gaml_hip_ctx* c, Staging& s, size_t bytes, void** host) {
-  int k = s.next;
-  s.next = (s.next + 1) % kRing;
-  if (s.armed[k]) { HIP_TRY(c, hipEventSynchronize(s.done[k])); s.armed[k] = false; }
-  if (!s.done[k]) HIP_TRY(c, hipEventCreateWithFlags(&s.done[k], hipEventDisableTiming));
-  HIP_TRY(c, s.host[k].reserve(bytes));
-  *host = s.host[k].p;
+  int k = 0;
+  HIP_TRY(c, s.acquire(&k));
+  HIP_TRY(c, s.slot[k].reserve(bytes));
+  *host = s.slot[k].p;
   return k;
 }
 int stage_release(gaml_hip_ctx* c, Staging& s, int k, hipStream_t st) {
   // a blocking call returns after the device is done with the slot: no event (a marker packet and ~1.5 us of host time)
   if (c->host_results) return 0;
-  HIP_TRY(c, hipEventRecord(s.done[k], st));
-  s.armed[k] = true;
+  HIP_TRY(c, s.release(k, st));
   return 0;
 }
 
@@ -107,12 +104,12 @@ __global__ __launch_bounds__(kBlock) void stage_copy_kernel(const int4* __restri
 int stage_upload(gaml_hip_ctx* c, Staging& s, int k, void* dst, size_t bytes, hipStream_t st) {
   if (bytes == 0) return 0;
   if (KNOB(c, UPLOAD_ROUTE) == GAML_HIP_UPLOAD_MEMCPY || (bytes & 15) || bytes > ((size_t)1 << 30)) {
-    HIP_TRY(c, hipMemcpyAsync(dst, s.host[k].p, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(dst, s.slot[k].p, bytes, hipMemcpyHostToDevice, st));
     return 0;
   }
   const int n16 = (int)(bytes / 16);
   hipLaunchKernelGGL(stage_copy_kernel, dim3((unsigned)std::min(64, (n16 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                     (const int4*)s.host[k].dev, (int4*)dst, n16);
+                     (const int4*)s.slot[k].dev, (int4*)dst, n16);
   HIP_TRY(c, hipGetLastError());
   return 0;
 }
@@ -138,13 +135,13 @@ int collect_events(gaml_hip_ctx* c) {
   return 0;
 }
 
-int take_events(gaml_hip_ctx* c, std::pair<hipEvent_t, hipEvent_t>** out) {
+int take_events(gaml_hip_ctx* c, EventPair** out) {
   if (c->ev_used == c->ev_pool.size() && c->ev_pool.size() >= 2048) { if (int e = collect_events(c)) return e; }
   if (c->ev_used == c->ev_pool.size()) {
-    hipEvent_t a, b;
-    HIP_TRY(c, hipEventCreate(&a));
-    HIP_TRY(c, hipEventCreate(&b));
-    c->ev_pool.emplace_back(a, b);
+    EventPair p;
+    HIP_TRY(c, p.first.ensure(hipEventDefault));
+    HIP_TRY(c, p.second.ensure(hipEventDefault));
+    c->ev_pool.push_back(std::move(p));
   }
   if (c->ev_call.size() < c->ev_pool.size()) c->ev_call.resize(c->ev_pool.size(), 0);
   c->ev_call[c->ev_used] = c->eval_serial;
@@ -471,9 +468,9 @@ int gaml_hip_create(gaml_hip_ctx** out, int device) {
     }
     {  // the evaluations' stream: highest priority (a table build runs beside it on a stream of the lowest, paired_tables.hip.h)
       int lo = 0, hi = 0;
-      if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi) != hipSuccess) return GAML_HIP_EHIP;
+      if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || hipStreamCreateWithPriority(&c->stream.s, hipStreamNonBlocking, hi) != hipSuccess) return GAML_HIP_EHIP;
     }
-    if (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess) return GAML_HIP_EHIP;
+    if (hipStreamCreateWithFlags(&c->aux_stream.s, hipStreamNonBlocking) != hipSuccess) return GAML_HIP_EHIP;
     // large BAR (every MI300-class part): per-call tables are written by the host straight into device memory
     // (paired_launch.hip.h: Arena). GAML_HIP_DIRECT_WRITE=0 forces the staged path.
     int large_bar = 0;
@@ -508,29 +505,8 @@ void gaml_hip_destroy(gaml_hip_ctx* c) {
     // stream-ordered evaluation went to (all streams of the device: the caller's is not ours to name), then the communicator
     (void)hipDeviceSynchronize();
     if (c->comm) { gaml::comm_destroy(c->comm); c->comm = nullptr; }
-    auto drop_stage = [](Staging& s) { for (int k = 0; k < kRing; k++) { s.host[k].release(); if (s.done[k]) (void)hipEventDestroy(s.done[k]); } };
-    for (auto& s : c->singles) { s->dev.first.release(); s->dev.extra.release(); s->dev.pows.release(); s->lens.release(); s->probs.release(); s->tabs.release(); s->occ_arena.release(); s->red.release(); s->multi.release(); s->dev.pool.release(); s->dev.aln.release(); s->td.release(); drop_stage(s->stage); }
-    for (auto& s : c->paireds) {
-      if (s->rebuild.stream) (void)hipStreamDestroy(s->rebuild.stream);
-      if (s->rebuild.done) (void)hipEventDestroy(s->rebuild.done);
-      if (s->rebuild.mark) (void)hipEventDestroy(s->rebuild.mark);
-      s->tab.release(); s->rebuild.tab.release(); s->scratch.release();
-      for (int m = 0; m < 2; m++) { s->dev[m].first.release(); s->dev[m].extra.release(); s->dev[m].pows.release(); s->dev[m].aln.release(); s->dev[m].pool.release(); s->dev[m].lens.release();
-                                    s->dl_rec[m].release(); s->sp_rng[m].release(); s->sp_rec[m].release(); }
-      s->dl_slot.release(); s->dl_spill.release(); s->sp_slot.release(); s->dstate.release(); s->dl_bins.release(); s->dl_bin_count.release(); s->dl_blk_tot.release(); s->dl_wlist.release(); s->h_dstate.release(); s->lcode.release(); s->len_combo_dev.release(); s->combo_tabs.release(); s->memo.release();
-      drop_stage(s->stage_pool); s->h_part_sum.release(); s->h_part_zero.release(); s->h_timeline.release();
-      s->probs.release(); s->tabs.release(); s->arena.release(); s->persist.release(); s->occdev.release(); s->cov_bits.release(); s->bad.release(); s->cov_multi.release(); s->h_bad.release(); if (s->ev_tables) (void)hipEventDestroy(s->ev_tables); if (s->ev_ovf) (void)hipEventDestroy(s->ev_ovf);
-      s->red.release(); s->adv.release();
-    }
-    for (auto& s : c->pacbios) { s->d_lens.release(); s->rec_off.release(); s->rec_walk.release(); s->rec_logp.release(); s->walk_count.release(); s->logprobs.release(); s->red.release(); drop_stage(s->stage);
-      s->d_bases.release(); s->dp.release(); s->sweep.release(); s->multi.release(); }
-    c->packed.release(); c->packed_host.release(); c->batch_dev.release(); c->batch_host.release(); c->aln_scratch.release();
-    c->aln_small[0].release(); c->aln_small[1].release(); c->fetch_host.release(); c->warm_buf.release();
-    for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   }
-  delete c;
+  delete c;  // (the device still current: every buffer, event and stream goes with its owner, the context's streams last -- resource.hip.h)
 }
 
 const char* gaml_hip_last_error(const gaml_hip_ctx* c) {
@@ -885,12 +861,8 @@ int gaml_hip_eval_pacbio_finish_async(gaml_hip_ctx* c, int32_t i, const void* in
   PbSweepDev& d = s.sweep;
   const size_t want = (size_t)std::max<int64_t>(1, pb.n_node + n_intervals) * sizeof(int4);
   if (want > d.all.cap) {  // the node intervals move along
-    DevBuf bigger;
     HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, bigger.reserve(want));
-    if (pb.n_node) HIP_TRY(c, hipMemcpy(bigger.p, d.all.p, (size_t)pb.n_node * sizeof(int4), hipMemcpyDeviceToDevice));
-    d.all.release();
-    d.all = bigger;
+    HIP_TRY(c, d.all.regrow(std::max<size_t>(want + want / 4, 256), (size_t)pb.n_node * sizeof(int4)));
   }
   // all ranks' alignment intervals behind the node intervals (this rank's own are among them)
   if (n_intervals > 0) HIP_TRY(c, hipMemcpyAsync(d.all.as<int4>() + pb.n_node, intervals, (size_t)n_intervals * sizeof(int4), hipMemcpyDeviceToDevice, st));
@@ -1540,10 +1512,10 @@ int gaml_hip_set_event_timing(gaml_hip_ctx* c, int on) {
     // hipEventCreate lands inside a caller's timed region
     HIP_TRY(c, hipSetDevice(c->device));
     while (c->ev_pool.size() < 2048) {
-      hipEvent_t a, b;
-      HIP_TRY(c, hipEventCreate(&a));
-      HIP_TRY(c, hipEventCreate(&b));
-      c->ev_pool.emplace_back(a, b);
+      EventPair p;
+      HIP_TRY(c, p.first.ensure(hipEventDefault));
+      HIP_TRY(c, p.second.ensure(hipEventDefault));
+      c->ev_pool.push_back(std::move(p));
     }
   }
   return GAML_HIP_OK;

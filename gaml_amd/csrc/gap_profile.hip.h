@@ -220,7 +220,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
       if (r.bw[mt] > P.cap_w[mt] || ps.image[mt].multi_off.size() > P.cap_lo[mt] || ps.image[mt].multi.size() > P.cap_m[mt]) return 1;  // (the update above made room: cannot happen)
       r.chg_bytes[mt] = align16(r.bw[mt]);
     }
-    r.stride = align16(P.bytes);
+    r.stride = align16(P.blk.cap);
     r.L = paired_persist_layout(P);
     if (r.cov) {
       const PairedPrep& p0 = r.prep[0];
@@ -249,7 +249,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
       if (int e = arena_commit(c, ps.arena, r.slot, 0, st)) return e;  // (direct route: drains the write-combining buffers)
       GapTabArgs ta;
       memset(&ta, 0, sizeof(ta));
-      paired_tab_geometry(ta, ps, ps.arena.dev[r.slot], r.stride, r.bw, (unsigned char*)ps.arena.dev[r.slot] + r.stride * (size_t)chunk, r.chg_bytes);
+      paired_tab_geometry(ta, ps, ps.arena.slot[r.slot].dev, r.stride, r.bw, (unsigned char*)ps.arena.slot[r.slot].dev + r.stride * (size_t)chunk, r.chg_bytes);
       for (int mt = 0; mt < 2; mt++) {
         ta.n_occ[mt] = (int)ps.image[mt].occ12.size();
         ta.n_lists[mt] = ps.image[mt].multi_off.empty() ? 0 : (int)ps.image[mt].multi_off.size() - 1;
@@ -276,7 +276,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
       hipLaunchKernelGGL(gap_tables_kernel, dim3((unsigned)n + 1, r.cov ? 3 : 2), dim3(1024), 0, st, ta);
       HIP_TRY(c, hipGetLastError());
       const unsigned char* chg[2] = {ta.chg[0], ta.chg[1]};
-      if (int e = launch_paired_multi(c, ps, 0, n, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.dev[r.slot], r.stride, st, chg)) return e;
+      if (int e = launch_paired_multi(c, ps, 0, n, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.slot[r.slot].dev, r.stride, st, chg)) return e;
     }
     if (int e = multi_wait(c)) return e;
     multi_collect(c, n, part.data(), any_cov);

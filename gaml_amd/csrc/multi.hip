@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "resource.hip.h"
 
 namespace gaml {
 
@@ -76,19 +77,7 @@ Rccl* rccl() {
   return &r;
 }
 
-struct DevMem {  // grow-only device buffer (the caller synchronises the stream that may still read the old one)
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes, hipStream_t st) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) return e; (void)hipFree(p); p = nullptr; cap = 0; }
-    const size_t want = std::max<size_t>(256, bytes + bytes / 4);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+using detail::DevBuf;  // (reserved with the stream that may still read the old buffer: it drains first)
 
 }  // namespace
 
@@ -98,7 +87,7 @@ struct CommState {
   int mode = 0;       // hot-path exchange: 0 all-gather of the ranks' partials, summed in RANK ORDER by every rank; 1 all-reduce(sum)
   bool dead = false;  // aborted after a time-out: every later evaluation fails at once
   double timeout_s = 60.0;
-  DevMem part, small, own, all, pack, gath;  // partials (f64) + 2 status words | maxima, sizes | this rank's map / intervals | the gathered ones | the gathered intervals, contiguous | every rank's partials
+  DevBuf part, small, own, all, pack, gath;  // partials (f64) + 2 status words | maxima, sizes | this rank's map / intervals | the gathered ones | the gathered intervals, contiguous | every rank's partials
 };
 
 // one block writes two doubles behind a rank's partials: its status for the exchange (no host-to-device copy command)
@@ -124,7 +113,6 @@ static double comm_timeout_s() {
 void comm_destroy(CommState* s) {
   if (!s) return;
   if (s->comm && !s->dead && rccl()->CommDestroy) (void)rccl()->CommDestroy(s->comm);  // (an aborted communicator is gone already)
-  s->part.release(); s->small.release(); s->own.release(); s->all.release(); s->pack.release(); s->gath.release();
   delete s;
 }
 
@@ -397,7 +385,7 @@ struct MultiState {
   bool have_comm = false;   // every shard holds a communicator (distinct devices, RCCL loaded)
   int exchange = 0;         // 0: pinned-host partials summed in rank order by the calling thread; 1: RCCL all-reduce
   // host-exchange scratch, per shard
-  struct KidBufs { DevMem part, own, all; };
+  struct KidBufs { DevBuf part, own, all; };
   std::vector<KidBufs> bufs;
   std::string err;
 
@@ -418,7 +406,7 @@ void multi_destroy(MultiState* m) {
   if (!m->kids.empty()) {
     m->run_all([m](int k, gaml_hip_ctx* kid) {
       auto& b = m->bufs[k];
-      if (ctx_device(kid) >= 0) { (void)hipStreamSynchronize(ctx_stream(kid)); b.part.release(); b.own.release(); b.all.release(); }
+      if (ctx_device(kid) >= 0) { (void)hipStreamSynchronize(ctx_stream(kid)); b.part.reset(); b.own.reset(); b.all.reset(); }  // (on the shard's thread, before its context goes)
       gaml_hip_destroy(kid);  // incl. its communicator
       return 0;
     });

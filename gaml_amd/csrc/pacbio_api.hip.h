@@ -50,9 +50,9 @@ int run_pacbio_dp(gaml_hip_ctx* c, DpDev& d, const std::string& both, const unsi
   a.dbg_hi = dbg_rows > 0 ? d.dbg.as<int32_t>() + dbg_rows : nullptr;
   a.n_jobs = (int32_t)nj;
   a.log_match = log_match; a.log_mismatch = log_mismatch;
-  hipEvent_t ev0, ev1;
-  HIP_TRY(c, hipEventCreate(&ev0));
-  HIP_TRY(c, hipEventCreate(&ev1));
+  Event ev0, ev1;
+  HIP_TRY(c, ev0.ensure(hipEventDefault));
+  HIP_TRY(c, ev1.ensure(hipEventDefault));
   HIP_TRY(c, hipEventRecord(ev0, st));
   constexpr int kLanes = 16;  // lanes per alignment (one DPP row): 15 columns per chunk cover a typical row in one step
   const unsigned grid = (unsigned)(((int64_t)nj * kLanes + 255) / 256);
@@ -68,8 +68,6 @@ int run_pacbio_dp(gaml_hip_ctx* c, DpDev& d, const std::string& both, const unsi
   }
   HIP_TRY(c, hipStreamSynchronize(st));
   HIP_TRY(c, hipEventElapsedTime(kernel_ms, ev0, ev1));
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
   if (cells_out) { *cells_out = 0; for (long long v : cells) *cells_out += v; }
   return GAML_HIP_OK;
 }
@@ -336,8 +334,6 @@ int gaml_hip_debug_sam_logprob(gaml_hip_ctx* c, const char* target, int32_t targ
                         std::vector<std::pair<const uint32_t*, size_t>>(1, std::make_pair((const uint32_t*)ops.data(), ops.size())),
                         2 * dp_row_stride(shape.max_width), std::log(1.0 - 4 * mismatch_prob), std::log(mismatch_prob), logprob_out, &ms, nullptr,
                         band_lo, band_hi, want_band ? n_rows : 0);
-  dev.release();
-  d_read.release();
   return e ? e : n_rows;
 }
 

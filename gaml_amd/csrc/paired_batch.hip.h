@@ -112,7 +112,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
     // bring the copy up to the images (made here if no blocking call has yet; entries changed by a call that did not go through it)
     if (paired_persist_stale(ps)) { if (int e = paired_persist_update(c, ps, 2.0, st)) return e; }
     PerSet& r = per[i];
-    r.stride = align16(P.bytes);
+    r.stride = align16(P.blk.cap);
     if (ps.cfg.penalty_constant > 0) {
       // the layout [slot_base | path_base | start_off | starts] of the largest set (paired_cov_ints: slots there are or the batch
       // may add, paths, one start per path entry at most), written through the BAR like the thresholds
@@ -154,8 +154,8 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
       memcpy(d_off, r.patch_off.data(), (2 * (size_t)upto + 1) * sizeof(int));
       if (int e = arena_commit(c, ps.arena, r.slot, 0, st)) return e;  // (direct route: drains the write-combining buffers)
       BatchTabArgs ta;
-      char* dev_tail = (char*)ps.arena.dev[r.slot] + r.stride * (size_t)n;
-      paired_tab_geometry(ta, ps, ps.arena.dev[r.slot], r.stride, r.bw,
+      char* dev_tail = (char*)ps.arena.slot[r.slot].dev + r.stride * (size_t)n;
+      paired_tab_geometry(ta, ps, ps.arena.slot[r.slot].dev, r.stride, r.bw,
                           (unsigned char*)dev_tail + r.tail_fixed + (size_t)(r.launches & 1) * (r.chg_bytes[0] + r.chg_bytes[1]), r.chg_bytes);  // (the other launch's may still be read)
       ta.patches = (const BatchPatch*)dev_tail;
       ta.patch_off = (const int*)(dev_tail + align16(kPatchCap * sizeof(BatchPatch)));
@@ -165,7 +165,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
       hipLaunchKernelGGL(batch_tables_kernel, dim3((unsigned)(upto - first) + 1, 2), dim3(1024), 0, st, ta);
       HIP_TRY(c, hipGetLastError());
       const unsigned char* chg[2] = {ta.chg[0], ta.chg[1]};
-      if (int e = launch_paired_multi(c, ps, first, upto - first, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.dev[r.slot], r.stride, st,
+      if (int e = launch_paired_multi(c, ps, first, upto - first, r.Ls.data(), r.prep.data(), tls, (const char*)ps.arena.slot[r.slot].dev, r.stride, st,
                                       KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_NO_CAPTURE ? nullptr : chg)) return e;  // every set resolves every pair (A/B)
     }
     return 0;
@@ -224,7 +224,7 @@ static int batch_chunk_patched(gaml_hip_ctx* c, int n, const int32_t* paths, con
   // the device is done with the resident copies: they follow the images (now the last set's)
   for (size_t i = 0; i < nps; i++) {
     PairedSet& ps = *c->paireds[i];
-    char* occ[2] = {(char*)ps.persist.dev + ps.persist.off_occ[0], (char*)ps.persist.dev + ps.persist.off_occ[1]};
+    char* occ[2] = {(char*)ps.persist.blk.dev + ps.persist.off_occ[0], (char*)ps.persist.blk.dev + ps.persist.off_occ[1]};
     for (int mt = 0; mt < 2; mt++)
       for (int32_t w : per[i].touched[mt]) memcpy(occ[mt] + (size_t)w * sizeof(Occ12), &ps.image[mt].occ12[w], sizeof(Occ12));
   }
@@ -266,7 +266,7 @@ static int batch_chunk_fast(gaml_hip_ctx* c, int n, const int32_t* paths, const 
       for (int k = first; k < upto; k++) paired_pack_thresholds(ps, per[i].L[(size_t)k].tfloor_off, (double)(2 * (tls[k] == 0 ? 1 : tls[k])), per[i].wp + (size_t)k * per[i].stride);
       // (the staged route copies the regions written so far; the direct route only drains the write-combining buffers)
       if (int e = arena_commit(c, ps.arena, per[i].slot, per[i].stride * (size_t)upto, st)) return e;
-      if (int e = launch_paired_multi(c, ps, first, upto - first, per[i].L.data(), per[i].prep.data(), tls, (const char*)ps.arena.dev[per[i].slot], per[i].stride, st)) return e;
+      if (int e = launch_paired_multi(c, ps, first, upto - first, per[i].L.data(), per[i].prep.data(), tls, (const char*)ps.arena.slot[per[i].slot].dev, per[i].stride, st)) return e;
     }
     return 0;
   };

@@ -215,41 +215,33 @@ void paired_pack(const PairedSet& s, const PairedPrep& p, const PairedLayout& L,
 // Otherwise (or UPLOAD_ROUTE != 0): pinned staging slot + hipMemcpyAsync (MEMCPY) / copy kernel (COPY_KERNEL).
 // ---------------------------------------------------------------------------------------------------------
 int arena_acquire(gaml_hip_ctx* c, Arena& A, size_t bytes, hipStream_t st, int* slot_out, char** write_ptr) {
-  const int k = A.next;
-  A.next = (A.next + 1) % kRing;
-  if (A.armed[k]) { HIP_TRY(c, hipEventSynchronize(A.done[k])); A.armed[k] = false; }
-  if (!A.done[k]) HIP_TRY(c, hipEventCreateWithFlags(&A.done[k], hipEventDisableTiming));
+  int k = 0;
+  HIP_TRY(c, A.acquire(&k));
+  HostBlock& b = A.slot[k];
   const bool direct = c->direct_write && KNOB(c, UPLOAD_ROUTE) == 0;
-  if (bytes > A.cap[k] || A.direct[k] != direct) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (A.dev[k]) { HIP_TRY(c, hipFree(A.dev[k])); A.dev[k] = nullptr; A.cap[k] = 0; }
-    const size_t want = std::max<size_t>(bytes + bytes / 2, (size_t)1 << 20);
-    if (direct) HIP_TRY(c, hipExtMallocWithFlags(&A.dev[k], want, hipDeviceMallocFinegrained));
-    else HIP_TRY(c, hipMalloc(&A.dev[k], want));
-    A.cap[k] = want; A.direct[k] = direct;
-  }
-  if (direct) *write_ptr = (char*)A.dev[k];
-  else { HIP_TRY(c, A.host[k].reserve(bytes)); *write_ptr = (char*)A.host[k].p; }
+  if (bytes > b.cap || b.direct != direct) HIP_TRY(c, b.reserve(std::max<size_t>(bytes + bytes / 2, (size_t)1 << 20), direct, st));
+  if (direct) *write_ptr = (char*)b.dev;
+  else { HIP_TRY(c, b.host.reserve(bytes)); *write_ptr = (char*)b.host.p; }
   *slot_out = k;
   return 0;
 }
 
 // after packing: make the bytes visible to the kernels launched next on `st`
 int arena_commit(gaml_hip_ctx* c, Arena& A, int k, size_t bytes, hipStream_t st) {
-  if (A.direct[k]) { _mm_sfence(); return 0; }  // drain the write-combining buffers; the doorbell write of the launch orders behind them
+  const HostBlock& b = A.slot[k];
+  if (b.direct) { _mm_sfence(); return 0; }  // drain the write-combining buffers; the doorbell write of the launch orders behind them
   if (bytes == 0) return 0;
-  if (KNOB(c, UPLOAD_ROUTE) == GAML_HIP_UPLOAD_MEMCPY || (bytes & 15)) { HIP_TRY(c, hipMemcpyAsync(A.dev[k], A.host[k].p, bytes, hipMemcpyHostToDevice, st)); return 0; }
+  if (KNOB(c, UPLOAD_ROUTE) == GAML_HIP_UPLOAD_MEMCPY || (bytes & 15)) { HIP_TRY(c, hipMemcpyAsync(b.dev, b.host.p, bytes, hipMemcpyHostToDevice, st)); return 0; }
   const int n16 = (int)(bytes / 16);
   hipLaunchKernelGGL(stage_copy_kernel, dim3((unsigned)std::min(64, (n16 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                     (const int4*)A.host[k].dev, (int4*)A.dev[k], n16);
+                     (const int4*)b.host.dev, (int4*)b.dev, n16);
   HIP_TRY(c, hipGetLastError());
   return 0;
 }
 
 int arena_release(gaml_hip_ctx* c, Arena& A, int k, hipStream_t st) {
   if (c->host_results) return 0;  // a blocking call returns after the device is done with the slot: no event
-  HIP_TRY(c, hipEventRecord(A.done[k], st));
-  A.armed[k] = true;
+  HIP_TRY(c, A.release(k, st));
   return 0;
 }
 
@@ -269,8 +261,8 @@ PairedLayout paired_persist_layout(const PairedSet::Persist& P) {
   PairedLayout L;
   L.tfloor_off = P.off_tfloor;
   L.l0 = OccLayout{P.off_occ[0], P.off_lo[0], P.off_m[0], P.off_lo[1] /* unused */};
-  L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.bytes};
-  L.sb_off = L.pb_off = L.so_off = L.st_off = 0; L.total = P.bytes;
+  L.l1 = OccLayout{P.off_occ[1], P.off_lo[1], P.off_m[1], P.blk.cap};
+  L.sb_off = L.pb_off = L.so_off = L.st_off = 0; L.total = P.blk.cap;
   return L;
 }
 
@@ -280,7 +272,7 @@ PairedLayout paired_persist_layout(const PairedSet::Persist& P) {
 template <class TabArgs>
 void paired_tab_geometry(TabArgs& ta, const PairedSet& s, void* regions, size_t stride, const size_t* entries, unsigned char* chg, const size_t* chg_bytes) {
   const PairedSet::Persist& P = s.persist;
-  ta.base = (const char*)P.dev;
+  ta.base = (const char*)P.blk.dev;
   ta.regions = (char*)regions;
   ta.stride = stride;
   for (int mt = 0; mt < 2; mt++) {
@@ -292,12 +284,12 @@ void paired_tab_geometry(TabArgs& ta, const PairedSet& s, void* regions, size_t 
   ta.chg[0] = chg; ta.chg[1] = chg + chg_bytes[0];
 }
 
-// cov_L (penalty_constant > 0): receives where this call's coverage layout sits in the copy (offsets from Persist::dev)
+// cov_L (penalty_constant > 0): receives where this call's coverage layout sits in the copy (offsets from Persist::blk)
 int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream_t st, const PairedPrep* p = nullptr, PairedLayout* cov_L = nullptr) {
   PairedSet::Persist& P = s.persist;
   OccImage* im = s.image;
   size_t need_w[2], need_lo[2], need_m[2];
-  bool relayout = P.dev == nullptr;
+  bool relayout = P.blk.dev == nullptr;
   const size_t need_cov = cov_L ? paired_cov_ints(*p) : 0;
   if (need_cov > P.cap_cov) relayout = true;
   for (int mt = 0; mt < 2; mt++) {
@@ -323,17 +315,12 @@ int paired_persist_update(gaml_hip_ctx* c, PairedSet& s, double two_T, hipStream
     // (the coverage layout: a few ints per path and contig, written whole per call; room for many times the paths there are)
     P.cap_cov = need_cov ? std::max<size_t>(4 * need_cov, 16384) : P.cap_cov;  // (a batch brings the copy up to date without a layout: the room stays)
     P.off_cov = at; at = align16(at + P.cap_cov * sizeof(int32_t));
-    if (at > P.bytes) {
-      HIP_TRY(c, hipStreamSynchronize(st));
-      if (P.dev) { HIP_TRY(c, hipFree(P.dev)); P.dev = nullptr; }
-      HIP_TRY(c, hipExtMallocWithFlags(&P.dev, at, hipDeviceMallocFinegrained));
-      P.bytes = at;
-    }
+    if (at > P.blk.cap) HIP_TRY(c, P.blk.reserve(at, true, st));
     // windows to come read as absent: every table entry all ones, once per layout (the image only ever grows)
-    for (int mt = 0; mt < 2; mt++) memset((char*)P.dev + P.off_occ[mt], 0xff, P.cap_w[mt] * sizeof(Occ12));
+    for (int mt = 0; mt < 2; mt++) memset((char*)P.blk.dev + P.off_occ[mt], 0xff, P.cap_w[mt] * sizeof(Occ12));
     full = true;
   }
-  char* wp = (char*)P.dev;  // write-only: device memory behind the PCIe BAR
+  char* wp = (char*)P.blk.dev;  // write-only: device memory behind the PCIe BAR
   P.last_bytes = 0;
   for (int mt = 0; mt < 2; mt++) {
     OccImage& t = im[mt];
@@ -471,7 +458,7 @@ void paired_set_view(const PairedSet& s, const PairedLayout& L, const char* aren
 }
 // ... and the same of the resident copy
 void paired_persist_view(const PairedSet& s, int32_t total_len, SetDev& sd) {
-  paired_set_view(s, paired_persist_layout(s.persist), (const char*)s.persist.dev, total_len, sd);
+  paired_set_view(s, paired_persist_layout(s.persist), (const char*)s.persist.blk.dev, total_len, sd);
 }
 
 void paired_apply_set(PairedArgs& a, const SetDev& sd) {
@@ -542,7 +529,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
   s.occdev.check_dup = s.occdev.taken;
   if (s.occdev.taken) {
     // device route: occ_scatter_kernel (queued in pass 2) builds this call's tables; only the thresholds go through the BAR
-    paired_pack_thresholds(s, s.persist.off_tfloor, (double)(2 * tl), (char*)s.persist.dev);
+    paired_pack_thresholds(s, s.persist.off_tfloor, (double)(2 * tl), (char*)s.persist.blk.dev);
     _mm_sfence();
     paired_persist_view(s, total_len, sd);
     for (int mt = 0; mt < 2; mt++) sd.occ12[mt] = occdev_table(s, mt);
@@ -551,7 +538,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     if (int e = paired_persist_update(c, s, (double)(2 * tl), st, &p, cov ? &L : nullptr)) return e;
     paired_persist_view(s, total_len, sd);
     c->prof[6] = (double)s.persist.last_bytes;  // entries written (all of them after a relayout) + the coverage layout
-    if (cov) arena = (const char*)s.persist.dev;  // the call's coverage layout sits in the resident copy too
+    if (cov) arena = (const char*)s.persist.blk.dev;  // the call's coverage layout sits in the resident copy too
   } else {
     L = paired_layout(s, p);
     char* wp = nullptr;
@@ -559,7 +546,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     paired_pack(s, p, L, wp);
     paired_pack_thresholds(s, L.tfloor_off, (double)(2 * tl), wp);
     if (int e = arena_commit(c, s.arena, slot, L.total, st)) return e;
-    arena = (const char*)s.arena.dev[slot];
+    arena = (const char*)s.arena.slot[slot].dev;
     paired_set_view(s, L, arena, total_len, sd);
     c->prof[6] = (double)L.total;
   }
@@ -598,7 +585,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     s.timeline_waves = a.total_blocks * (kBlock / 64);
   }
 
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+  EventPair* ev = nullptr;
   if (n > 0) {
     // HIP events bracket the dominant kernel only (bench.py's roofline; rocprofv3 must agree)
     if (c->event_timing && (c->event_tick++ % c->event_every) == 0) { if (int e = take_events(c, &ev)) return e; }
@@ -731,7 +718,7 @@ int launch_paired_multi(gaml_hip_ctx* c, PairedSet& s, int first, int n_sets, co
   }
   paired_apply_set(a, ms.set[0]);  // (fields every set overrides; harmless defaults)
   if (cov) { a.cov_bits = ms.set[0].cov_bits; a.path_base = ms.set[0].slot_base; }
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+  EventPair* ev = nullptr;
   if (c->event_timing && (c->event_tick++ % c->event_every) == 0) { if (int e = take_events(c, &ev)) return e; }
   hipEvent_t e0 = ev ? ev->first : nullptr, e1 = ev ? ev->second : nullptr;
   const dim3 grid(a.total_blocks), block(kBlock);

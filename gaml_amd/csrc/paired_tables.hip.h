@@ -26,12 +26,7 @@ int pool_reserve(gaml_hip_ctx* c, PairedSet& s, int mt, int64_t want) {
   if ((size_t)want * sizeof(int4) <= d.pool.cap) return 0;
   // growing moves the pool: everything that reads it must be through (cold: the pool leaves room for twice what it holds)
   HIP_TRY(c, hipDeviceSynchronize());
-  const size_t bytes = std::max<size_t>((size_t)want * 2, 1 << 16) * sizeof(int4);
-  void* np = nullptr;
-  HIP_TRY(c, hipMalloc(&np, bytes));
-  if (d.pool.p && d.pool_n) HIP_TRY(c, hipMemcpy(np, d.pool.p, (size_t)d.pool_n * sizeof(int4), hipMemcpyDeviceToDevice));
-  if (d.pool.p) HIP_TRY(c, hipFree(d.pool.p));
-  d.pool.p = np; d.pool.cap = bytes;
+  HIP_TRY(c, d.pool.regrow(std::max<size_t>((size_t)want * 2, 1 << 16) * sizeof(int4), (size_t)d.pool_n * sizeof(int4)));
   return 0;
 }
 
@@ -619,11 +614,16 @@ int paired_delta_reset(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
 // ---- rebuilds ----------------------------------------------------------------------------------------------------------
 int paired_build_continue(gaml_hip_ctx* c, PairedSet& s, bool rest);
 // the build's stream: lowest priority -- its workgroups yield to the evaluations' (whose stream has the highest)
-hipError_t paired_build_stream(hipStream_t* out) {
-  int lo = 0, hi = 0;
-  hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);  // (numerically: lo is the LEAST urgent)
-  if (e != hipSuccess) return e;
-  return hipStreamCreateWithPriority(out, hipStreamNonBlocking, lo);
+// ... and the two events of a build beside the evaluations, made once (never in an annealing call: paired_prereserve)
+hipError_t paired_build_stream(TableRebuild& rb) {
+  if (!rb.stream.s) {
+    int lo = 0, hi = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);  // (numerically: lo is the LEAST urgent)
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&rb.stream.s, hipStreamNonBlocking, lo);
+    if (e != hipSuccess) return e;
+  }
+  hipError_t e = rb.done.ensure();
+  return e != hipSuccess ? e : rb.mark.ensure();
 }
 
 // Every buffer the record tables, their builds and their delta lists need, for a pool of up to two records per read and mate
@@ -662,14 +662,10 @@ int paired_prereserve(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
     if (int e = paired_reserve_delta(c, s)) return e;
   }
   for (int k = 0; k < kRing; k++) {  // (pinned allocations take milliseconds: not in the annealing call that first stages a window list)
-    HIP_TRY(c, s.stage_pool.host[k].reserve((size_t)1 << 20));
-    if (!s.stage_pool.done[k]) HIP_TRY(c, hipEventCreateWithFlags(&s.stage_pool.done[k], hipEventDisableTiming));
+    HIP_TRY(c, s.stage_pool.slot[k].reserve((size_t)1 << 20));
+    HIP_TRY(c, s.stage_pool.done[k].ensure());
   }
-  if (KNOB(c, REBUILD_ON_CALLER) == 0) {
-    if (!rb.stream) HIP_TRY(c, paired_build_stream(&rb.stream));
-    if (!rb.done) HIP_TRY(c, hipEventCreateWithFlags(&rb.done, hipEventDisableTiming));
-    if (!rb.mark) HIP_TRY(c, hipEventCreateWithFlags(&rb.mark, hipEventDisableTiming));
-  }
+  if (KNOB(c, REBUILD_ON_CALLER) == 0) HIP_TRY(c, paired_build_stream(rb));
   if (first) {
     DevBuf* all[] = {&s.dev[0].pool, &s.dev[1].pool, &B.k_in, &B.k_out, &B.k_tmp, &B.v_in, &B.v_tmp, &B.hist, &B.v_sorted[0], &B.v_sorted[1], &B.rstart[0], &B.rstart[1],
                      &B.rend[0], &B.rend[1], &B.one[0], &B.one[1], &B.cl, &B.sidx, &B.more[0], &B.more[1], &B.start[0], &B.start[1], &B.tiles, &B.wins[0], &B.wins[1], &B.peer0,
@@ -736,9 +732,7 @@ int paired_start_async_rebuild(gaml_hip_ctx* c, PairedSet& s, hipStream_t st) {
   }
   rb.retired = false;
   const double t1 = now_us();
-  if (!rb.stream) HIP_TRY(c, paired_build_stream(&rb.stream));
-  if (!rb.done) HIP_TRY(c, hipEventCreateWithFlags(&rb.done, hipEventDisableTiming));
-  if (!rb.mark) HIP_TRY(c, hipEventCreateWithFlags(&rb.mark, hipEventDisableTiming));
+  HIP_TRY(c, paired_build_stream(rb));
   // the build reads the pool as the calling stream has filled it, and overwrites buffers earlier launches may still read
   HIP_TRY(c, hipEventRecord(rb.mark, st));
   HIP_TRY(c, hipStreamWaitEvent(rb.stream, rb.mark, 0));

@@ -92,7 +92,7 @@ int single_chunk_launch(gaml_hip_ctx* c, SgChunk& ch, int n, const int32_t* path
     a.ticket = M.ticket.as<unsigned>();
     a.out = (double*)M.out.dev;
     a.n_reads = (double)n_reads;
-    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    EventPair* ev = nullptr;
     if (c->event_timing && (c->event_tick++ % c->event_every) == 0) { if (int e = take_events(c, &ev)) return e; }
     hipExtLaunchKernelGGL(single_score_multi_kernel, dim3((unsigned)grid), dim3(kBlock), 0, st, ev ? ev->first : nullptr, ev ? ev->second : nullptr, 0, a);
     HIP_TRY(c, hipGetLastError());
