@@ -88,6 +88,10 @@ class Knob(enum.IntEnum):
     DELTA_SPILL_CAP = 24
     TAKE_OVER_AFTER = 25
     REBUILD_DIVISOR = 26
+    GRID_CAP_CLASS2 = 27
+    GRID_CAP_DELTA = 28
+    GRID_CAP_OVERFLOW = 29
+    GRID_CAP_SETS = 30
 
 
 KNOB_COUNT = len(Knob)

@@ -47,6 +47,15 @@ int grid_for(int64_t n) {
   int64_t b = (n + kBlock - 1) / kBlock;
   return (int)std::max<int64_t>(1, std::min<int64_t>(b, kMaxBlocks));
 }
+// ... and the development build's caps on it (gaml_hip_debug.h: they only lower a grid; the release build's GRID_FOR is
+// grid_for, its GRID_CAPPED the built-in value)
+#ifdef GAML_HIP_DEV
+#define GRID_CAPPED(c, i, built_in) (KNOB(c, i) > 0 ? std::min<int64_t>(KNOB(c, i), (built_in)) : (int64_t)(built_in))
+#define GRID_FOR(c, n) ((int)GRID_CAPPED(c, GRID_CAP_SETS, grid_for(n)))
+#else
+#define GRID_CAPPED(c, i, built_in) (built_in)
+#define GRID_FOR(c, n) grid_for(n)
+#endif
 
 // take the next staging slot; waits only if the device is kRing evaluations behind
 #ifdef GAML_HIP_DEV
@@ -889,11 +898,11 @@ int gaml_hip_eval_coverage_finish_async(gaml_hip_ctx* c, int32_t i, const void* 
   PairedSet& s = *c->paireds[pc.paired_idx];
   if (pc.args.total_words > 0) {
     if (n_maps > 0) {
-      hipLaunchKernelGGL(or_maps_kernel, dim3(grid_for(pc.args.total_words)), dim3(kBlock), 0, st, s.cov_bits.as<uint32_t>(),
+      hipLaunchKernelGGL(or_maps_kernel, dim3(GRID_FOR(c, pc.args.total_words)), dim3(kBlock), 0, st, s.cov_bits.as<uint32_t>(),
                          (const uint32_t*)maps, n_maps, pc.args.total_words);
       HIP_TRY(c, hipGetLastError());
     }
-    hipLaunchKernelGGL(coverage_sweep_kernel, dim3(grid_for(pc.args.total_words)), dim3(kBlock), 0, st, pc.args);
+    hipLaunchKernelGGL(coverage_sweep_kernel, dim3(GRID_FOR(c, pc.args.total_words)), dim3(kBlock), 0, st, pc.args);
     HIP_TRY(c, hipGetLastError());
   }
   // every rank computes the same bad_bases; one of them contributes it to the all-reduce(sum) of the partials

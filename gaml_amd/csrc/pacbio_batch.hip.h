@@ -89,7 +89,7 @@ int pacbio_chunk_launch(gaml_hip_ctx* c, PbChunk& ch, int n, const int32_t* path
     a.floor_b = std::log(std::exp(s.cfg.min_prob_per_base));  // logdouble(exp(k))
     a.n = (int)n_reads; a.n_sets = n;
     a.logprobs = s.logprobs.as<double>();
-    const int grid = grid_for(n_reads * 64);  // one wave per read: pacbio_score_kernel's grid
+    const int grid = GRID_FOR(c, n_reads * 64);  // one wave per read: pacbio_score_kernel's grid
     a.part_sum = M.part_sum.as<double>(); a.part_zero = M.part_zero.as<int>(); a.part_stride = grid;
     a.ticket = M.ticket.as<unsigned>();
     a.out = (double*)M.out.dev;

@@ -228,7 +228,7 @@ int launch_pacbio(gaml_hip_ctx* c, PacbioSet& s, const std::vector<Walk>& paths_
   a.n_reads = (double)n; a.bad_bases = 0.0;  // (with a penalty: the sweep below stores it)
   if (n > 0) {
     int64_t threads = n * 64;  // one wave per read
-    hipLaunchKernelGGL(pacbio_score_kernel, dim3(grid_for(threads)), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(pacbio_score_kernel, dim3(GRID_FOR(c, threads)), dim3(kBlock), 0, st, a);
     HIP_TRY(c, hipGetLastError());
   } else {
     HIP_TRY(c, hipMemsetAsync(out4, 0, 4 * sizeof(double), st));

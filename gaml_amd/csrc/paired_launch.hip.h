@@ -426,11 +426,11 @@ void paired_base_args(gaml_hip_ctx* c, PairedSet& s, PairedArgs& a, GridPlan& gp
   // 128 blocks 11.4 us, 192: 10.1, 224-256: 9.8-9.9, 320: 10.2)
   const int cap1 = KNOB(c, GRID_CAP_CLASS1) > 0 ? KNOB(c, GRID_CAP_CLASS1) : cap0 / 3;
   gp.blocks1 = (int)std::max<int64_t>(1, std::min<int64_t>((n01 - n0 + kBlock - 1) / kBlock, cap1));
-  gp.blocks2 = (int)std::max<int64_t>(1, std::min<int64_t>((n_main - n01 + kBlock - 1) / kBlock, kMaxBlocks / 4));
+  gp.blocks2 = (int)std::max<int64_t>(1, std::min<int64_t>((n_main - n01 + kBlock - 1) / kBlock, GRID_CAPPED(c, GRID_CAP_CLASS2, kMaxBlocks / 4)));
   // delta pairs: one lane per pair behind the table classes
-  gp.blocks_d = nd ? (int)std::min<int64_t>(((int64_t)nd + kBlock - 1) / kBlock, 1024) : 0;
+  gp.blocks_d = nd ? (int)std::min<int64_t>(((int64_t)nd + kBlock - 1) / kBlock, GRID_CAPPED(c, GRID_CAP_DELTA, 1024)) : 0;
   gp.main_blocks = gp.blocks0 + gp.blocks1 + gp.blocks2 + gp.blocks_d;
-  gp.ovf_blocks = ovf_total > 0 ? (int)std::min<int64_t>((ovf_total + 3) / 4, kOvfMaxBlocks) : 0;
+  gp.ovf_blocks = ovf_total > 0 ? (int)std::min<int64_t>((ovf_total + 3) / 4, GRID_CAPPED(c, GRID_CAP_OVERFLOW, kOvfMaxBlocks)) : 0;
   gp.total_blocks = gp.main_blocks + gp.ovf_blocks;
   a.blocks0a = gp.blocks0a;
   a.blocks0 = gp.blocks0;
@@ -627,7 +627,7 @@ int launch_paired(gaml_hip_ctx* c, PairedSet& s, PairedPrep& p, int32_t total_le
     c->pending_cov.push_back(gaml_hip_ctx::PendingCov{idx, paired_cov_args(s, p, L, arena), out4});
   } else if (cov && n > 0 && p.total_bits > 0) {
     const CovArgs ca = paired_cov_args(s, p, L, arena);
-    hipLaunchKernelGGL(coverage_sweep_kernel, dim3(grid_for(ca.total_words)), dim3(kBlock), 0, st, ca);
+    hipLaunchKernelGGL(coverage_sweep_kernel, dim3(GRID_FOR(c, ca.total_words)), dim3(kBlock), 0, st, ca);
     HIP_TRY(c, hipGetLastError());
   }
   if (cov && n > 0 && !c->defer_cov) {
@@ -741,7 +741,7 @@ int launch_paired_multi(gaml_hip_ctx* c, PairedSet& s, int first, int n_sets, co
       v = paired_cov_args(s, preps[g], L[g], arena + (size_t)g * stride);  // but the set's own bitmap and counter
       v.bits = ms.set[k].cov_bits;
       v.bad = counters + k;
-      ca.block_off[k + 1] = ca.block_off[k] + (v.total_words > 0 ? grid_for(v.total_words) : 0);  // (the empty assembly: no blocks, its counter stays 0)
+      ca.block_off[k + 1] = ca.block_off[k] + (v.total_words > 0 ? GRID_FOR(c, v.total_words) : 0);  // (the empty assembly: no blocks, its counter stays 0)
     }
     if (ca.block_off[n_sets] > 0) {
       hipLaunchKernelGGL(coverage_sweep_multi_kernel, dim3((unsigned)ca.block_off[n_sets]), dim3(kBlock), 0, st, ca);

@@ -87,7 +87,7 @@ int single_chunk_launch(gaml_hip_ctx* c, SgChunk& ch, int n, const int32_t* path
       a.two_T[k] = (double)(2 * (t == 0 ? 1 : t));
     }
     a.probs = s.probs.as<double>();
-    const int grid = grid_for(n_reads);  // single_score_kernel's grid
+    const int grid = GRID_FOR(c, n_reads);  // single_score_kernel's grid
     a.part_sum = M.part_sum.as<double>(); a.part_zero = M.part_zero.as<int>(); a.part_stride = grid;
     a.ticket = M.ticket.as<unsigned>();
     a.out = (double*)M.out.dev;

@@ -104,7 +104,7 @@ int launch_single(gaml_hip_ctx* c, SingleSet& s, const std::vector<Walk>& paths,
   a.ticket = s.red.ticket.as<unsigned>(); a.out = out4;
   a.n_reads = (double)n;
   if (n > 0) {
-    hipLaunchKernelGGL(single_score_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(single_score_kernel, dim3(GRID_FOR(c, n)), dim3(kBlock), 0, st, a);
     HIP_TRY(c, hipGetLastError());
   } else {
     HIP_TRY(c, hipMemsetAsync(out4, 0, 4 * sizeof(double), st));

@@ -97,7 +97,14 @@ enum gaml_hip_knob {
   GAML_HIP_KNOB_DELTA_SPILL_CAP = 24,       /* n > 0: the delta store's spill area holds n long lists, 16 n records per mate (read when the store is reserved: set it before the first evaluation) */
   GAML_HIP_KNOB_TAKE_OVER_AFTER = 25,       /* n > 0: a build beside the evaluations takes over n evaluations after its start (default 96) */
   GAML_HIP_KNOB_REBUILD_DIVISOR = 26,       /* n > 1: tables are rebuilt when the delta lists pass pairs / n, at least 256 (default: pairs / 8, at least 4,096) */
-  GAML_HIP_KNOB_COUNT = 27
+  /* the block counts of the scoring launches: a cap can only LOWER a grid (0: the built-in rule, n > 0: min(that rule, n)) -- the
+   * partial buffers are sized from the built-in maxima. With the three GRID_CAP knobs above they let a test of a few thousand pairs
+   * run every class's stride loop for several rounds (tests/test_gpu_grid_split.py). */
+  GAML_HIP_KNOB_GRID_CAP_CLASS2 = 27,       /* n > 0: most blocks of the 3-4-record class */
+  GAML_HIP_KNOB_GRID_CAP_DELTA = 28,        /* n > 0: most blocks of the delta pairs */
+  GAML_HIP_KNOB_GRID_CAP_OVERFLOW = 29,     /* n > 0: most wave-per-pair blocks */
+  GAML_HIP_KNOB_GRID_CAP_SETS = 30,         /* n > 0: most blocks of every launch sized by grid_for: the single-end and PacBio scorers, their multi-set forms, the coverage sweeps */
+  GAML_HIP_KNOB_COUNT = 31
 };
 /* the values of the knobs that choose between routes (0 = the default, in every one) */
 enum gaml_hip_aligner_route {
