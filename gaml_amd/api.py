@@ -92,6 +92,7 @@ class Knob(enum.IntEnum):
     GRID_CAP_DELTA = 28
     GRID_CAP_OVERFLOW = 29
     GRID_CAP_SETS = 30
+    PACBIO_SWEEP_CAP = 31
 
 
 KNOB_COUNT = len(Knob)
@@ -335,6 +336,13 @@ def _load():
         L.gaml_hip_single_stats.argtypes = [vp, C.c_int, _i64p]
         L.gaml_hip_set_single_onepass.argtypes = [vp, C.c_int32]
         L.gaml_hip_get_single_onepass.argtypes = [vp]
+    if hasattr(L, "gaml_hip_set_pacbio_penalty_onepass"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_set_pacbio_penalty_onepass.argtypes = [vp, C.c_int32]
+        L.gaml_hip_get_pacbio_penalty_onepass.argtypes = [vp]
+        L.gaml_hip_pacbio_penalty_stats.argtypes = [vp, C.c_int, _i64p]
+    if hasattr(L, "gaml_hip_debug_pacbio_batch_bad_bases"):  # development build only
+        L.gaml_hip_debug_pacbio_batch_bad_bases.argtypes = [vp, C.c_int, C.c_void_p, C.c_int32]
+        L.gaml_hip_debug_pacbio_batch_bad_bases.restype = C.c_int32
     if hasattr(L, "gaml_hip_set_single_device"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_set_single_device.argtypes = [vp, C.c_int32]
         L.gaml_hip_get_single_device.argtypes = [vp]
@@ -943,6 +951,27 @@ class Context:
         self._check(_lib.gaml_hip_single_stats(self._h, rs, out))
         return {"windows": int(out[0]), "records": int(out[1]), "table_bytes": int(out[2]), "multi_launches": int(out[3])}
 
+    def set_pacbio_penalty_onepass(self, on):
+        """Let PacBio sets with a coverage penalty go along on calc_prob_batch's one-pass routes
+        (gaml_hip_set_pacbio_penalty_onepass); off by default, or what GAML_HIP_PACBIO_PENALTY_BATCH=onepass said when the
+        context was made. Same values either way."""
+        if not hasattr(_lib, "gaml_hip_set_pacbio_penalty_onepass"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_set_pacbio_penalty_onepass")
+        self._check(_lib.gaml_hip_set_pacbio_penalty_onepass(self._h, 1 if on else 0))
+
+    def get_pacbio_penalty_onepass(self) -> bool:
+        return hasattr(_lib, "gaml_hip_get_pacbio_penalty_onepass") and _lib.gaml_hip_get_pacbio_penalty_onepass(self._h) == 1
+
+    def pacbio_penalty_stats(self, rs):
+        """{chunks, block_contigs, chain_contigs, memo_paths} of a PacBio set (gaml_hip_pacbio_penalty_stats), cumulative: chunks
+        scored with its penalty on the one-pass routes, contigs swept one per block, contigs swept through the general chain,
+        distinct paths of a chunk whose bad_bases the memo had."""
+        if not hasattr(_lib, "gaml_hip_pacbio_penalty_stats"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_pacbio_penalty_stats")
+        out = np.zeros(4, np.int64)
+        self._check(_lib.gaml_hip_pacbio_penalty_stats(self._h, rs, out))
+        return {"chunks": int(out[0]), "block_contigs": int(out[1]), "chain_contigs": int(out[2]), "memo_paths": int(out[3])}
+
     def set_single_device(self, on):
         """Single-end sets: windows aligned on the device in batches, read-major tables built there by kernels
         (gaml_hip_set_single_device); off by default, or what GAML_HIP_SINGLE_DEVICE=1 set when the context was made."""
@@ -1051,6 +1080,14 @@ class Context:
         n = self._check(_lib.gaml_hip_debug_batch_bad_bases(self._h, rs, None, 0))
         out = np.zeros(max(1, n), np.int64)
         self._check(_lib.gaml_hip_debug_batch_bad_bases(self._h, rs, out.ctypes.data, n))
+        return out[:n].tolist()
+
+    def debug_pacbio_batch_bad_bases(self, rs):
+        """bad_bases of PacBio set rs for every path set of the last calc_prob_batch, in its order, whichever route
+        (development build)."""
+        n = self._check(_lib.gaml_hip_debug_pacbio_batch_bad_bases(self._h, rs, None, 0))
+        out = np.zeros(max(1, n), np.int64)
+        self._check(_lib.gaml_hip_debug_pacbio_batch_bad_bases(self._h, rs, out.ctypes.data, n))
         return out[:n].tolist()
 
     def debug_tables_check(self, rs):

@@ -364,7 +364,9 @@ struct PbSweepDev {
 // what a path contributes to a PacBio evaluation (pacbio_enumerate): its cached sub-walks in the order the reference
 // meets them (graph.cc:2438-2454), each with the path coordinate it starts at, and the lookups that found nothing
 struct PbHit { int32_t walk, begin; };
-struct PbEnum { std::vector<PbHit> hits; int64_t misses = 0; int32_t len = 0; };
+// `bad`: the path's bad_bases (CalcScoreForPacbio's sum is over the paths of the call, each swept on its own), -1 until a
+// chunk of the one-pass routes has swept it; holds as long as the memo entry does
+struct PbEnum { std::vector<PbHit> hits; int64_t misses = 0; int32_t len = 0; int64_t bad = -1; };
 
 // a PacBio set's side of gaml_hip_calc_prob_batch (pacbio_batch.hip.h)
 struct PbMulti {
@@ -374,6 +376,11 @@ struct PbMulti {
   DevBuf part_sum, part_zero, ticket;  // per set and block; a ticket of its own (pacbio_score_multi_kernel)
   PinBuf out;       // {sum, floored, 0, reads} per set, written by the last block
   int64_t launches = 0;
+  // a set with a penalty (gaml_hip_set_pacbio_penalty_onepass): the chunk's paths without a memoised value, one contig each
+  DevBuf sweep_in;  // headers | node intervals | occurrences of the contigs pacbio_path_sweep_kernel takes, staged as one block
+  DevBuf bad;       // per swept contig: the block-per-contig kernel's first, the general chain's behind them
+  PinBuf bad_host;  // ... handed over behind the sweeps (pacbio_store_bad_kernel)
+  int64_t penalty_stats[4] = {0, 0, 0, 0};  // gaml_hip_pacbio_penalty_stats
 };
 
 struct PacbioSet {
@@ -389,6 +396,7 @@ struct PacbioSet {
   DevBuf d_lens, rec_off, rec_walk, rec_logp, walk_count, logprobs;
   Reducer red;
   int64_t last_bad_bases = 0;
+  std::vector<int64_t> batch_bad;  // bad_bases per path set of the last gaml_hip_calc_prob_batch, whichever route (gaml_hip_debug_pacbio_batch_bad_bases)
   Staging stage;
   PbSweepDev sweep;
   PbMulti multi;
@@ -419,6 +427,8 @@ struct SetRef { int kind, idx; };
 inline bool gap_penalty_env() { const char* e = getenv("GAML_HIP_GAP_PENALTY"); return e && strcmp(e, "device") == 0; }
 // GAML_HIP_SINGLE_BATCH=onepass: what a new context's single_onepass starts as (read when the context is made)
 inline bool single_onepass_env() { const char* e = getenv("GAML_HIP_SINGLE_BATCH"); return e && strcmp(e, "onepass") == 0; }
+// GAML_HIP_PACBIO_PENALTY_BATCH=onepass: what a new context's pacbio_penalty_onepass starts as (read when the context is made)
+inline bool pacbio_penalty_onepass_env() { const char* e = getenv("GAML_HIP_PACBIO_PENALTY_BATCH"); return e && strcmp(e, "onepass") == 0; }
 // GAML_HIP_SINGLE_DEVICE=1: what a new context's single_device starts as (read when the context is made)
 inline bool single_device_env() { const char* e = getenv("GAML_HIP_SINGLE_DEVICE"); return e && strcmp(e, "1") == 0; }
 
@@ -481,6 +491,7 @@ struct gaml_hip_ctx {
   int64_t gap_stats[4] = {0, 0, 0, 0};
   bool gap_penalty_device = gap_penalty_env();  // penalised paired sets may take the gap profile's device route (gaml_hip_set_gap_penalty_device)
   bool single_onepass = single_onepass_env();  // single-end sets go along on the batch's one-pass routes (gaml_hip_set_single_onepass)
+  bool pacbio_penalty_onepass = pacbio_penalty_onepass_env();  // PacBio sets with a penalty go along on the batch's one-pass routes (gaml_hip_set_pacbio_penalty_onepass)
   bool single_device = single_device_env();  // single-end sets: windows aligned in device batches, read-major tables built by kernels (gaml_hip_set_single_device)
   AlnJob single_job;  // a single-end set's pending alignment batch (prepare_single_host): buffers kept from call to call, like aln_job
   std::vector<int32_t> gap_flat;

@@ -457,6 +457,14 @@ int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* c, int rs, int64_t* out, in
   return (int32_t)b.size();
 }
 
+int32_t gaml_hip_debug_pacbio_batch_bad_bases(gaml_hip_ctx* c, int rs, int64_t* out, int32_t cap) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 2 || cap < 0 || (cap > 0 && !out)) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const std::vector<int64_t>& b = c->pacbios[c->handles[rs].idx]->batch_bad;
+  for (size_t k = 0; k < b.size() && k < (size_t)cap; k++) out[k] = b[k];
+  return (int32_t)b.size();
+}
+
 // The LIVE record tables plus the live delta store (delta_dev.hip.h) against the host restatement, read by read. Looks and
 // changes nothing: no rebuild started or finished, no tables prepared (gaml_hip_debug_tables_check does all three) -- it
 // waits for the stream and copies back. The reference: build_pair_tables on a copy of the device pool over the windows the

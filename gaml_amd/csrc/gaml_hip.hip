@@ -1244,6 +1244,7 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* c, int32_t n_sets, const int32_t* pat
   if (n_sets == 0) return GAML_HIP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   for (auto& ps : c->paireds) { paired_images_refresh(*ps); ps->batch_bad.clear(); }  // the batch routes patch the images from the current set's
+  for (auto& pb : c->pacbios) pb->batch_bad.clear();
   const size_t ns = std::max<size_t>(1, c->handles.size());
   for (int32_t i = 0; i < n_sets; i++) if (set_offs[i + 1] < set_offs[i]) return fail(c, GAML_HIP_EINVAL, "set offsets must not decrease");
   int32_t done_sets = 0;
@@ -1294,6 +1295,8 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* c, int32_t n_sets, const int32_t* pat
     for (int32_t i = 0; i < n_sets; i++)
       for (size_t k = 0; k < order.size(); k++)
         if (order[k].kind == 1) c->paireds[order[k].idx]->batch_bad.push_back((int64_t)res[(size_t)i * 4 * ns + 4 * k + 2]);
+        // (a PacBio set: with the list the bookkeeping for gaml_hip_bad_bases -- the last set's, as after that many single calls and as the one-pass routes leave it)
+        else if (order[k].kind == 2) { PacbioSet& pb = *c->pacbios[order[k].idx]; pb.batch_bad.push_back((int64_t)res[(size_t)i * 4 * ns + 4 * k + 2]); pb.last_bad_bases = pb.batch_bad.back(); }
   }
   for (int32_t i = 0; i < n_sets; i++) {
     if (int e = combine(c, res + (size_t)i * 4 * ns, &probs_out[i], zeros_out ? zeros_out + (size_t)i * 2 * ns : nullptr, tls[i])) return e;
@@ -1449,6 +1452,21 @@ int gaml_hip_set_single_onepass(gaml_hip_ctx* c, int32_t on) {
   return GAML_HIP_OK;
 }
 int gaml_hip_get_single_onepass(const gaml_hip_ctx* c) { return c && c->single_onepass ? 1 : 0; }
+
+int gaml_hip_set_pacbio_penalty_onepass(gaml_hip_ctx* c, int32_t on) {
+  if (!c) return GAML_HIP_EINVAL;
+  c->pacbio_penalty_onepass = on != 0;  // (a host-only, multi-device or rank-per-process context only keeps the flag: its batches take other ways)
+  return GAML_HIP_OK;
+}
+int gaml_hip_get_pacbio_penalty_onepass(const gaml_hip_ctx* c) { return c && c->pacbio_penalty_onepass ? 1 : 0; }
+
+int gaml_hip_pacbio_penalty_stats(gaml_hip_ctx* c, int rs, int64_t* out4) {
+  MULTI_SHARD0(c);
+  if (!c || rs < 0 || rs >= (int)c->handles.size() || c->handles[rs].kind != 2 || !out4) return fail(c, GAML_HIP_EINVAL, "bad arguments");
+  const PbMulti& M = c->pacbios[c->handles[rs].idx]->multi;
+  for (int k = 0; k < 4; k++) out4[k] = M.penalty_stats[k];
+  return GAML_HIP_OK;
+}
 
 int gaml_hip_set_single_device(gaml_hip_ctx* c, int32_t on) {
   if (!c) return GAML_HIP_EINVAL;

@@ -68,8 +68,11 @@ int pacbio_sweep_prepare(gaml_hip_ctx* c, PacbioSet& s, const std::vector<int32_
   return 0;
 }
 
-// sort + running maximum + sweep over the n intervals in PbSweepDev::all; bad_bases (times `scale`) into out4[2]
-int pacbio_sweep_run(gaml_hip_ctx* c, PacbioSet& s, int64_t n, int32_t n_paths, hipStream_t st, double* out4, double scale) {
+// sort + running maximum + sweep over the n intervals in PbSweepDev::all; bad_bases (times `scale`) into out4[2]. With
+// per_contig (the batch's contigs that do not fit the block-per-contig kernel, pacbio_batch.hip.h) every contig's value is
+// added into per_contig[contig] instead, which the caller has zeroed on `st`; nothing is stored to out4 then.
+int pacbio_sweep_run(gaml_hip_ctx* c, PacbioSet& s, int64_t n, int32_t n_paths, hipStream_t st, double* out4, double scale,
+                     unsigned long long* per_contig = nullptr) {
   PbSweepDev& d = s.sweep;
   typedef unsigned long long u64;
   const size_t n1 = (size_t)std::max<int64_t>(1, n);
@@ -86,7 +89,7 @@ int pacbio_sweep_run(gaml_hip_ctx* c, PacbioSet& s, int64_t n, int32_t n_paths, 
     HIP_TRY(c, d.tmp.reserve(tmp_bytes));
     HIP_TRY(c, d.bad.reserve(sizeof(u64)));
   }
-  HIP_TRY(c, hipMemsetAsync(d.bad.p, 0, sizeof(u64), st));
+  if (!per_contig) HIP_TRY(c, hipMemsetAsync(d.bad.p, 0, sizeof(u64), st));
   if (n > 0) {
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
     hipLaunchKernelGGL(pacbio_sweep_keys_kernel, dim3(grid), dim3(256), 0, st, d.all.as<int4>(), (int)n, d.key_begin.as<u64>(), d.key_end.as<u64>(), d.pos.as<u64>());
@@ -99,10 +102,15 @@ int pacbio_sweep_run(gaml_hip_ctx* c, PacbioSet& s, int64_t n, int32_t n_paths, 
     HIP_TRY(c, rs_sort<u64>(d.pos.as<u64>(), d.pos_s.as<u64>(), tmp_keys, (const u64*)nullptr, (u64*)nullptr, (u64*)nullptr, (size_t)(2 * n), 0, end_bit, hist, st));
     HIP_TRY(c, rm_inclusive_max(d.key_end_s.as<u64>(), d.end_max.as<u64>(), (size_t)n, (u64*)((char*)d.tmp.p + off_rm), st));
     const unsigned grid2 = (unsigned)std::min<int64_t>((2 * n + 255) / 256, 1024);
-    hipLaunchKernelGGL(pacbio_sweep_kernel, dim3(grid2), dim3(256), 0, st, d.pos_s.as<u64>(), (int)(2 * n), d.key_begin_s.as<u64>(), d.end_max.as<u64>(), (int)n,
-                       d.in.as<int>(), s.cfg.step, d.bad.as<u64>());
+    if (per_contig)
+      hipLaunchKernelGGL(pacbio_sweep_kernel<true>, dim3(grid2), dim3(256), 0, st, d.pos_s.as<u64>(), (int)(2 * n), d.key_begin_s.as<u64>(), d.end_max.as<u64>(), (int)n,
+                         d.in.as<int>(), s.cfg.step, per_contig);
+    else
+      hipLaunchKernelGGL(pacbio_sweep_kernel<false>, dim3(grid2), dim3(256), 0, st, d.pos_s.as<u64>(), (int)(2 * n), d.key_begin_s.as<u64>(), d.end_max.as<u64>(), (int)n,
+                         d.in.as<int>(), s.cfg.step, d.bad.as<u64>());
     HIP_TRY(c, hipGetLastError());
   }
+  if (per_contig) return 0;
   hipLaunchKernelGGL(store_bad_bases_kernel, dim3(1), dim3(64), 0, st, d.bad.as<u64>(), out4, scale);
   HIP_TRY(c, hipGetLastError());
   return 0;

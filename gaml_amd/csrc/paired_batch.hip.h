@@ -16,14 +16,16 @@
 // own, one sweep dispatch per launch (launch_paired_multi); the wait is then a real stream wait, one per chunk.
 // PacBio sets without a coverage penalty go along as well, beside the paired sets or on their own: one dispatch of
 // pacbio_score_multi_kernel per set and chunk, enqueued before the paired sets are planned (pacbio_batch.hip.h); the wait is
-// a stream wait then too. A PacBio set with a penalty keeps the whole context on the sequential path. So does a single-end
-// set, unless the context's switch is on (gaml_hip_set_single_onepass, off by default): then single-end sets go along the
+// a stream wait then too. A PacBio set with a penalty keeps the whole context on the sequential path, unless the context's
+// switch is on (gaml_hip_set_pacbio_penalty_onepass, off by default): then the chunk sweeps the paths it has no bad_bases
+// for yet, one contig per block, behind that dispatch, and a set's bad_bases is the sum over its paths (pacbio_batch.hip.h).
+// A single-end set keeps the context sequential as well, unless the context's switch is on (gaml_hip_set_single_onepass, off by default): then single-end sets go along the
 // same way, one dispatch of single_score_multi_kernel per set and chunk, enqueued behind the PacBio one (single_batch.hip.h).
 // ---------------------------------------------------------------------------------------------------------
 static bool batch_fast_capable(const gaml_hip_ctx* c) {
   if (c->handles.empty() || KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_SEQUENTIAL) return false;  // force the sequential path (A/B, tools/)
   if (!c->single_onepass) for (auto& h : c->handles) if (h.kind == 0) return false;  // single-end sets go along only where the context says so (single_batch.hip.h)
-  for (auto& pb : c->pacbios) if (pb->cfg.penalty_constant > 0) return false;
+  if (!c->pacbio_penalty_onepass) for (auto& pb : c->pacbios) if (pb->cfg.penalty_constant > 0) return false;  // ... and so do penalised PacBio sets (pacbio_batch.hip.h)
   for (auto& ps : c->paireds) if (!paired_multi_capable(c, *ps)) return false;
   return true;
 }

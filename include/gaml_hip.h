@@ -302,8 +302,10 @@ int gaml_hip_calc_partials_async(gaml_hip_ctx* ctx, const int32_t* paths, const 
  * to 8 path sets per pass over the records instead: per chunk one launch per paired set over its records and one per
  * PacBio set over its cached alignments (occurrence counts of all sets of the chunk side by side per sub-walk), one wait.
  * Same values bit for bit, same gaml_hip_read_probs / gaml_hip_bad_bases / gaml_hip_pacbio_stats afterwards. A PacBio set
- * with a coverage penalty keeps the whole context on the path described above. So does a single-end set, unless the
- * context's switch is on (gaml_hip_set_single_onepass, off by default): then a single-end set goes along as well, one launch
+ * with a coverage penalty keeps the whole context on the path described above, unless the context's switch is on
+ * (gaml_hip_set_pacbio_penalty_onepass, off by default): then such a set goes along too, its chunk sweeping every path it
+ * has no bad_bases for yet once, one contig per block (gaml_hip_pacbio_penalty_stats counts). A single-end set keeps the
+ * context on that path as well, unless the context's switch is on (gaml_hip_set_single_onepass, off by default): then a single-end set goes along as well, one launch
  * per set and chunk over its read-major records with the occurrence tables of all sets of the chunk side by side
  * (gaml_hip_single_stats counts the chunks). Same values bit for bit with the switch on or off.
  *   paths / path_offs : all paths of all sets, concatenated (path k = paths[path_offs[k] .. path_offs[k+1]))
@@ -320,6 +322,22 @@ int gaml_hip_calc_prob_batch(gaml_hip_ctx* ctx, int32_t n_sets, const int32_t* p
  * either way; the gap-length search of such a context runs on its fallback, whose batches follow the switch. */
 int gaml_hip_set_single_onepass(gaml_hip_ctx* ctx, int32_t on);
 int gaml_hip_get_single_onepass(const gaml_hip_ctx* ctx);
+/* gaml_hip_set_pacbio_penalty_onepass / gaml_hip_get_pacbio_penalty_onepass: may PacBio sets with a coverage penalty go along
+ * on the one-pass routes of gaml_hip_calc_prob_batch (1) or does such a set keep its context on the sequential path (0, the
+ * default). Per context, any kind of context: host-only, in-process multi-device and rank-per-process contexts only keep the
+ * flag (their batches go other ways). A new context starts with 1 when the environment holds
+ * GAML_HIP_PACBIO_PENALTY_BATCH=onepass. Same values bit for bit either way, same gaml_hip_read_probs / gaml_hip_bad_bases /
+ * gaml_hip_pacbio_stats afterwards; the gap-length search of such a context runs on its fallback, whose batches follow the
+ * switch. With it on, bad_bases of a path set is the sum of its paths' values (CalcScoreForPacbio sweeps every path on its
+ * own): a chunk sweeps each distinct path it has no value for once and keeps the value with the path's memo entry until
+ * the record cache changes.
+ * gaml_hip_pacbio_penalty_stats: cumulative out4 = {chunks this set scored with its penalty on the one-pass routes, contigs
+ * swept one per block, contigs swept through the general chain (more intervals than a block takes), distinct paths of a
+ * chunk whose value the memo had}. GAML_HIP_EINVAL for a handle that is not a PacBio set; zeros on a host-only context;
+ * a multi-device context reports its first shard. */
+int gaml_hip_set_pacbio_penalty_onepass(gaml_hip_ctx* ctx, int32_t on);
+int gaml_hip_get_pacbio_penalty_onepass(const gaml_hip_ctx* ctx);
+int gaml_hip_pacbio_penalty_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
 /* gaml_hip_set_single_device / gaml_hip_get_single_device: are the windows of single-end sets aligned on the device, one
  * batch per path set that brings new ones, and their read-major record tables built there by kernels from a mirror of the
  * host's record pool (1), or does the host align window by window and build and upload the whole table whenever a window

@@ -104,7 +104,8 @@ enum gaml_hip_knob {
   GAML_HIP_KNOB_GRID_CAP_DELTA = 28,        /* n > 0: most blocks of the delta pairs */
   GAML_HIP_KNOB_GRID_CAP_OVERFLOW = 29,     /* n > 0: most wave-per-pair blocks */
   GAML_HIP_KNOB_GRID_CAP_SETS = 30,         /* n > 0: most blocks of every launch sized by grid_for: the single-end and PacBio scorers, their multi-set forms, the coverage sweeps */
-  GAML_HIP_KNOB_COUNT = 31
+  GAML_HIP_KNOB_PACBIO_SWEEP_CAP = 31,      /* n > 0: a contig goes to the block-per-contig sweep of a penalised PacBio set's chunk with up to min(n, 2048) intervals, larger ones through the general chain (default: 2048) */
+  GAML_HIP_KNOB_COUNT = 32
 };
 /* the values of the knobs that choose between routes (0 = the default, in every one) */
 enum gaml_hip_aligner_route {
@@ -196,6 +197,10 @@ int gaml_hip_debug_single_table_check(gaml_hip_ctx* ctx, int readset, int64_t* o
  * capture of unchanged pairs is always off for such a launch, so NO_CAPTURE equals 0 there), FULL_TABLES whole tables per set,
  * SEQUENTIAL one call per path set. */
 int32_t gaml_hip_debug_batch_bad_bases(gaml_hip_ctx* ctx, int readset, int64_t* out, int32_t cap);
+/* The same of PacBio set `readset` (0 for a set without coverage penalty): filled by the one-pass routes
+ * (gaml_hip_set_pacbio_penalty_onepass) and by the sequential path alike, so a test can hold route against route.
+ * GAML_HIP_EINVAL for a handle that is not a PacBio set. */
+int32_t gaml_hip_debug_pacbio_batch_bad_bases(gaml_hip_ctx* ctx, int readset, int64_t* out, int32_t cap);
 
 /* The LIVE record tables plus the live delta lists (gaml_amd/csrc/delta_dev.hip.h) of paired set `readset` against the host
  * restatement build_pair_tables, read by read, over the windows the tables and their lists took in. Inspects and changes

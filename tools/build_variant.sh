@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/build_variant.sh NAME [-DFLAG ...]: an A/B build of the library into build_ab/libgaml_hip_NAME.so (load it with
 # GAML_HIP_LIB=...), with the register / scratch use of the paired scoring kernels (the multi-set kernel's and the coverage
-# sweeps' and the gap profile's table kernel and the PacBio and single-end scorers and the single-end table build's kernels with LDS and scalar registers) and of the aligner's span and extension kernels (both instantiations) printed: a variant that spills to scratch is not worth a GPU run.
+# sweeps' and the gap profile's table kernel and the PacBio and single-end scorers and the PacBio coverage sweeps (the block-per-contig pacbio_path_sweep_kernel among them) and the single-end table build's kernels with LDS and scalar registers) and of the aligner's span and extension kernels (both instantiations) printed: a variant that spills to scratch is not worth a GPU run.
 set -e
 NAME=$1; shift
 HERE=$(cd "$(dirname "$0")/.." && pwd)
@@ -20,7 +20,7 @@ for b in re.split(r"remark: Function Name: ", t)[1:]:
     aln = re.search(r"(span_maxima_kernel|span_cands_kernel|extend_kernel|extend_pair2_kernel)ILi(\d+)E", name)  # the aligner's instantiations (aligner.hip.h)
     if aln: print(sys.argv[2], f"{aln.group(1)}<{aln.group(2)}>", "VGPR", g("VGPRs"), "SGPR", g("SGPRs"), "LDS", g(r"LDS Size \[bytes/block\]"), "scratch", g(r"ScratchSize \[bytes/lane\]"), "spillV", g("VGPRs Spill"), "spillS", g("SGPRs Spill"), "waves/SIMD", g(r"Occupancy \[waves/SIMD\]"))
     # the multi-set scoring kernel (template arguments: GEN, COV) and the coverage sweeps: LDS and scalar registers too
-    if "paired_score_multi_kernel" in name or "coverage_sweep" in name or "gap_tables_kernel" in name or "pacbio_score" in name or "single_score" in name or re.search(r"st_(clear|keys|heads|fill)_kernel", name):
+    if "paired_score_multi_kernel" in name or "coverage_sweep" in name or "gap_tables_kernel" in name or "pacbio_score" in name or "pacbio_path_sweep" in name or "pacbio_sweep_kernel" in name or "single_score" in name or re.search(r"st_(clear|keys|heads|fill)_kernel", name):
         print(sys.argv[2], name, "VGPR", g("VGPRs"), "SGPR", g("SGPRs"), "LDS", g(r"LDS Size \[bytes/block\]"), "scratch", g(r"ScratchSize \[bytes/lane\]"), "spillV", g("VGPRs Spill"), "spillS", g("SGPRs Spill"), "waves/SIMD", g(r"Occupancy \[waves/SIMD\]"))
     if "paired_score_kernel" not in name: continue
     print(sys.argv[2], name[22:60], "VGPR", g("VGPRs"), "scratch", g(r"ScratchSize \[bytes/lane\]"), "spillV", g("VGPRs Spill"), "spillS", g("SGPRs Spill"))
