@@ -328,6 +328,16 @@ def _load():
     if hasattr(L, "gaml_hip_set_gap_penalty_device"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_set_gap_penalty_device.argtypes = [vp, C.c_int32]
         L.gaml_hip_get_gap_penalty_device.argtypes = [vp]
+    if hasattr(L, "gaml_hip_set_gap_mixed_device"):  # absent from older A/B builds loaded through GAML_HIP_LIB
+        L.gaml_hip_set_gap_mixed_device.argtypes = [vp, C.c_int32]
+        L.gaml_hip_get_gap_mixed_device.argtypes = [vp]
+    if hasattr(L, "gaml_hip_debug_gap_single_table"):  # development build only
+        L.gaml_hip_debug_gap_single_table.argtypes = [vp, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+        L.gaml_hip_debug_gap_single_table.restype = C.c_int64
+        L.gaml_hip_debug_gap_pacbio_counts.argtypes = [vp, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+        L.gaml_hip_debug_gap_pacbio_counts.restype = C.c_int64
+        L.gaml_hip_debug_pacbio_gap_enum.argtypes = [vp, C.c_int, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.gaml_hip_debug_pacbio_gap_enum.restype = C.c_int64
     if hasattr(L, "gaml_hip_debug_timeline"):  # absent from older A/B builds loaded through GAML_HIP_LIB
         L.gaml_hip_debug_timeline.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64]
     if hasattr(L, "gaml_hip_pacbio_stats"):  # absent from older A/B builds loaded through GAML_HIP_LIB
@@ -700,6 +710,17 @@ class Context:
     def gap_penalty_device(self) -> bool:
         return hasattr(_lib, "gaml_hip_get_gap_penalty_device") and _lib.gaml_hip_get_gap_penalty_device(self._h) == 1
 
+    def set_gap_mixed_device(self, on):
+        """Let a context that holds single-end sets and / or PacBio sets without a coverage penalty take the gap profile's
+        device route (gaml_hip_set_gap_mixed_device); off by default, or what GAML_HIP_GAP_MIXED=device said when the context
+        was made. Same values either way."""
+        if not hasattr(_lib, "gaml_hip_set_gap_mixed_device"):
+            raise GamlHipError(ESTATE, "this library has no gaml_hip_set_gap_mixed_device")
+        self._check(_lib.gaml_hip_set_gap_mixed_device(self._h, 1 if on else 0))
+
+    def gap_mixed_device(self) -> bool:
+        return hasattr(_lib, "gaml_hip_get_gap_mixed_device") and _lib.gaml_hip_get_gap_mixed_device(self._h) == 1
+
     def set_single_onepass(self, on):
         """Let single-end sets go along on calc_prob_batch's one-pass routes (gaml_hip_set_single_onepass); off by default, or
         what GAML_HIP_SINGLE_BATCH=onepass said when the context was made. Same values either way."""
@@ -915,6 +936,41 @@ class Context:
         sl, st = np.zeros(max(1, n), np.int32), np.zeros(max(1, cnt[2]), np.int32)
         _lib.gaml_hip_debug_gap_cov_layout(self._h, rs, g, sb.ctypes.data, len(sb), pb.ctypes.data, so.ctypes.data, sl.ctypes.data, max(1, n), st.ctypes.data, len(st), cnt.ctypes.data)
         return {"slot_base": sb[:cnt[0]], "path_base": pb, "start_off": so, "starts": st[:cnt[2]], "slots": sl[:n], "total_bits": int(cnt[3])}
+
+    def debug_gap_single_table(self, rs, g) -> np.ndarray:
+        """debug_occurrences' rows for region g of the last mixed device pass of a gap profile: the table
+        gap_single_tables_kernel derived for that pass's g-th length (gaml_hip_debug_gap_single_table)."""
+        z = np.zeros(5, np.int32)
+        n = _lib.gaml_hip_debug_gap_single_table(self._h, rs, g, z.ctypes.data, 0)
+        if n < 0:
+            raise GamlHipError(int(n), "no single-end table of a mixed device gap pass: no such pass or region")
+        out = np.zeros(5 * max(1, n), np.int32)
+        _lib.gaml_hip_debug_gap_single_table(self._h, rs, g, out.ctypes.data, n)
+        return out.reshape(-1, 5)[:n]
+
+    def debug_gap_pacbio_counts(self, rs, g) -> np.ndarray:
+        """Column g of the count table of the last mixed device pass of a gap profile, one count per cached sub-walk
+        (gaml_hip_debug_gap_pacbio_counts)."""
+        z = np.zeros(1, np.int32)
+        n = _lib.gaml_hip_debug_gap_pacbio_counts(self._h, rs, g, z.ctypes.data, 0)
+        if n < 0:
+            raise GamlHipError(int(n), "no count table of a mixed device gap pass")
+        out = np.zeros(max(1, n), np.int32)
+        _lib.gaml_hip_debug_gap_pacbio_counts(self._h, rs, g, out.ctypes.data, n)
+        return out[:n]
+
+    def debug_pacbio_gap_enum(self, rs, path, gap_pos, length):
+        """(hits [n, 2] = sub-walk id, begin; misses) of the mixed route's split enumeration of one path with `length` in
+        its gap, in the reference's order (gaml_hip_debug_pacbio_gap_enum; the library checks it against the whole one)."""
+        p = np.ascontiguousarray(path, dtype=np.int32)
+        miss = C.c_int64()
+        z = np.zeros(2, np.int32)
+        n = _lib.gaml_hip_debug_pacbio_gap_enum(self._h, rs, p, len(p), gap_pos, length, z.ctypes.data, 0, C.byref(miss))
+        if n < 0:
+            raise GamlHipError(int(n), self.last_error() if n == -2 else "bad arguments")
+        out = np.zeros(2 * max(1, n), np.int32)
+        _lib.gaml_hip_debug_pacbio_gap_enum(self._h, rs, p, len(p), gap_pos, length, out.ctypes.data, n, C.byref(miss))
+        return out.reshape(-1, 2)[:n], int(miss.value)
 
     def debug_window_walk(self, rs, mate, wid) -> list:
         buf = np.zeros(64, np.int32)

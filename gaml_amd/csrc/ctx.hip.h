@@ -342,6 +342,8 @@ struct SingleSet {
   SgMulti multi;
   int64_t table_bytes = 0;  // occurrence tables staged by the last call or chunk (gaml_hip_single_stats)
   SingleTabDev td;
+  // where the last mixed device gap pass left its regions in occ_arena (gap_mixed.hip.h; gaml_hip_debug_gap_single_table)
+  struct GapTab { int n = 0; size_t region0 = 0, stride = 0, off_direct = 0, off_lo = 0, off_m = 0; int n_direct = 0, n_lo = 0, n_multi = 0; } gap_tab;
 };
 
 struct DpDev {  // device buffers of the PacBio banded DP
@@ -400,6 +402,11 @@ struct PacbioSet {
   Staging stage;
   PbSweepDev sweep;
   PbMulti multi;
+  // a gap profile on the mixed device route (gap_mixed.hip.h): per sub-walk its occurrences in what the lengths share, resident
+  // for the profile's passes; the record cache it was counted against; the columns of the last pass (gaml_hip_debug_gap_pacbio_counts)
+  DevBuf gap_core;
+  uint64_t gap_core_generation = ~0ull;
+  int gap_cols = 0;
   // cache-miss side (SAM ingestion): bases of this shard's reads and the name -> global id map
   bool have_reads = false;
   std::string bases;
@@ -425,6 +432,8 @@ struct SetRef { int kind, idx; };
 
 // GAML_HIP_GAP_PENALTY=device: what a new context's gap_penalty_device starts as (read when the context is made)
 inline bool gap_penalty_env() { const char* e = getenv("GAML_HIP_GAP_PENALTY"); return e && strcmp(e, "device") == 0; }
+// GAML_HIP_GAP_MIXED=device: what a new context's gap_mixed_device starts as (read when the context is made)
+inline bool gap_mixed_env() { const char* e = getenv("GAML_HIP_GAP_MIXED"); return e && strcmp(e, "device") == 0; }
 // GAML_HIP_SINGLE_BATCH=onepass: what a new context's single_onepass starts as (read when the context is made)
 inline bool single_onepass_env() { const char* e = getenv("GAML_HIP_SINGLE_BATCH"); return e && strcmp(e, "onepass") == 0; }
 // GAML_HIP_PACBIO_PENALTY_BATCH=onepass: what a new context's pacbio_penalty_onepass starts as (read when the context is made)
@@ -490,6 +499,7 @@ struct gaml_hip_ctx {
   // fallback, device passes}, and the path set with the base length in its gap (kept from call to call)
   int64_t gap_stats[4] = {0, 0, 0, 0};
   bool gap_penalty_device = gap_penalty_env();  // penalised paired sets may take the gap profile's device route (gaml_hip_set_gap_penalty_device)
+  bool gap_mixed_device = gap_mixed_env();  // contexts with single-end sets and / or PacBio sets without a penalty may take the gap profile's device route (gaml_hip_set_gap_mixed_device)
   bool single_onepass = single_onepass_env();  // single-end sets go along on the batch's one-pass routes (gaml_hip_set_single_onepass)
   bool pacbio_penalty_onepass = pacbio_penalty_onepass_env();  // PacBio sets with a penalty go along on the batch's one-pass routes (gaml_hip_set_pacbio_penalty_onepass)
   bool single_device = single_device_env();  // single-end sets: windows aligned in device batches, read-major tables built by kernels (gaml_hip_set_single_device)

@@ -14,9 +14,15 @@
 // - bits(len) (a multiple of 32, not d), every region behind it moves by dbits, and the edited path's contig starts behind
 // the gap move by d. Marks need nothing new: a lane marks at slot_base[slot] + shift + position. Such a set takes the device
 // route only where the context asks for it (gaml_hip_set_gap_penalty_device / GAML_HIP_GAP_PENALTY=device).
+// Single-end sets and PacBio sets without a coverage penalty go along where the context asks for that
+// (gaml_hip_set_gap_mixed_device / GAML_HIP_GAP_MIXED=device; gap_mixed.hip.h): a single-end set's tables of every length are
+// derived from ONE host-built table (every rank behind the gap moves, the later paths' too), a PacBio set's count columns from
+// one enumeration per profile plus the sub-walks that contain the gap entry. A PacBio set WITH a penalty keeps its context
+// on the fallback whatever gaml_hip_set_pacbio_penalty_onepass says: its contig sweeps would have to run per length.
 //
 //   gap_tables_kernel     region g of an arena slot := the resident tables, those shift words + (lens[g] - base); for a
 //                         penalised set a third grid row: region g's coverage layout := the resident one by the rules above
+//   gap_mixed_plan / _launch / _collect   the other kinds' side of a profile and of a pass (gap_mixed.hip.h)
 //   gap_profile_device    plan the set once with the base length, then per pass of up to kMaxSets lengths: thresholds
 //                         through the BAR, gap_tables_kernel, paired_score_multi_kernel (launch_paired_multi, unchanged;
 //                         a penalised set: every length a PairedPrep with its own total_bits, bitmaps and sweep as a batch's);
@@ -25,6 +31,7 @@
 //   gap_profile_fallback  the same lengths as path sets of gaml_hip_calc_prob_batch / collective gaml_hip_calc_prob calls
 //   gaml_hip_fix_gap_length  the search, its evaluations taken from passes of lengths chosen before they are needed
 #pragma once
+#include "gap_mixed.hip.h"
 
 namespace gaml {
 
@@ -147,8 +154,18 @@ bool gap_device_capable(const gaml_hip_ctx* c) {
   // (gaml_hip_set_gap_penalty_device); otherwise such a context searches through the fallback (whose multi-length steps are
   // batches, one pass each)
   if (!c->gap_penalty_device) for (auto& ps : c->paireds) if (ps->cfg.penalty_constant > 0) return false;
-  for (auto& h : c->handles) if (h.kind != 1) return false;  // (the batch routes take PacBio sets along; the tables this route derives are the paired sets')
-  return batch_fast_capable(c);
+  bool others = false;
+  for (auto& h : c->handles) if (h.kind != 1) others = true;
+  if (!others) return batch_fast_capable(c);
+  // single-end and PacBio sets: their tables and count columns are derived per pass too (gap_mixed.hip.h), where the context
+  // asks for it (gaml_hip_set_gap_mixed_device). A PacBio set with a coverage penalty stays on the fallback whatever
+  // gaml_hip_set_pacbio_penalty_onepass says: every length would need the contig sweeps of its own coordinates. The route
+  // launches single_score_multi_kernel itself: gaml_hip_set_single_onepass, which governs batches, is not asked.
+  if (!c->gap_mixed_device) return false;
+  for (auto& pb : c->pacbios) if (pb->cfg.penalty_constant > 0) return false;
+  if (KNOB(c, BATCH_ROUTE) == GAML_HIP_BATCH_SEQUENTIAL) return false;
+  for (auto& ps : c->paireds) if (!paired_multi_capable(c, *ps)) return false;
+  return true;
 }
 
 // The device route. c->gap_flat / gap_offs hold the path set with `base_len` in the gap. Returns 1 when the set cannot go
@@ -235,6 +252,10 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     { const PairedPrep one = r.prep[0]; r.prep.assign((size_t)chunk, one); }  // every length: the same windows, lists and records
     if (int e = arena_acquire(c, ps.arena, r.stride * (size_t)chunk + r.chg_bytes[0] + r.chg_bytes[1], st, &r.slot, &r.wp)) return e;
   }
+  // the sets of the other kinds (none unless gaml_hip_set_gap_mixed_device let the context in): one host table / one
+  // enumeration per profile; a set that cannot go hands the profile to the fallback before anything reached its bookkeeping
+  GapMixed mixed(c);
+  if (int e = gap_mixed_plan(c, mixed, path_id, gap_pos, base_len, chunk, st)) return e;
   c->pending_open = false;
   const size_t ns = std::max<size_t>(1, c->handles.size());
   std::vector<double> part((size_t)kMaxSets * 4 * ns);
@@ -242,6 +263,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     const int n = std::min<int32_t>(chunk, n_lens - done);
     int32_t tls[kMaxSets];
     for (int k = 0; k < n; k++) tls[k] = tl0 + (lens[done + k] - base_len);  // (the caller checked that every total fits)
+    if (int e = gap_mixed_launch(c, mixed, lens + done, n, st)) return e;  // (before the paired sets' work, as batch_chunk_patched orders them)
     for (size_t i = 0; i < nps; i++) {
       PairedSet& ps = *c->paireds[i];
       PerSet& r = per[i];
@@ -280,6 +302,7 @@ int gap_profile_device(gaml_hip_ctx* c, int32_t n_paths, int32_t path_id, int32_
     }
     if (int e = multi_wait(c)) return e;
     multi_collect(c, n, part.data(), any_cov);
+    gap_mixed_collect(c, mixed, n, lens[done + n - 1], part.data());
     for (int k = 0; k < n; k++) {
       const int32_t at = done + k;
       if (int e = combine(c, part.data() + (size_t)k * 4 * ns, &probs_out[at], zeros_out ? zeros_out + (size_t)at * 2 * ns : nullptr, tls[k])) return e;
@@ -418,6 +441,13 @@ int gaml_hip_set_gap_penalty_device(gaml_hip_ctx* c, int32_t on) {
   return GAML_HIP_OK;
 }
 int gaml_hip_get_gap_penalty_device(const gaml_hip_ctx* c) { return c && c->gap_penalty_device ? 1 : 0; }
+
+int gaml_hip_set_gap_mixed_device(gaml_hip_ctx* c, int32_t on) {
+  if (!c) return GAML_HIP_EINVAL;
+  c->gap_mixed_device = on != 0;  // (a context the device route never serves only keeps the flag: gap_device_capable)
+  return GAML_HIP_OK;
+}
+int gaml_hip_get_gap_mixed_device(const gaml_hip_ctx* c) { return c && c->gap_mixed_device ? 1 : 0; }
 
 int gaml_hip_gap_stats(gaml_hip_ctx* c, int64_t* out4) {
   if (!c || !out4) return GAML_HIP_EINVAL;

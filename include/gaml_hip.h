@@ -395,7 +395,18 @@ int64_t gaml_hip_advice_candidates(gaml_hip_ctx* ctx, int readset, const int32_t
  * gaml_hip_set_gap_penalty_device / gaml_hip_get_gap_penalty_device: may paired sets with a coverage penalty take the
  *   device route (1) or not (0, the default). Per context, any kind of context: one the device route never serves only
  *   keeps the flag. A new context starts with 1 when the environment holds GAML_HIP_GAP_PENALTY=device. Same values on
- *   both routes. */
+ *   both routes.
+ * gaml_hip_set_gap_mixed_device / gaml_hip_get_gap_mixed_device: may a context that holds single-end sets and / or PacBio
+ *   sets without a coverage penalty -- beside paired sets or on their own -- take the device route (1) or not (0, the
+ *   default). With 1 a profile builds ONE single-end occurrence table on the host (the set with lens[0]) and derives every
+ *   other length's on the device, enumerates the edited path's PacBio sub-walks once and per length only those that contain
+ *   the gap entry, and scores up to 8 lengths per pass with the batch's multi-set kernels; it does not depend on
+ *   gaml_hip_set_single_onepass. What takes which route with the switch on: paired, single-end and unpenalised PacBio sets
+ *   the device route; a PacBio set with penalty_constant > 0 (whatever gaml_hip_set_pacbio_penalty_onepass says), a
+ *   penalised paired set without gaml_hip_set_gap_penalty_device, several devices, rank-per-process and host-only contexts
+ *   the fallback. Per context, any kind of context: one the device route never serves only keeps the flag. A new context
+ *   starts with 1 when the environment holds GAML_HIP_GAP_MIXED=device. Same values on both routes; a PacBio set's `misses`
+ *   (gaml_hip_pacbio_stats) count every length a pass scored, those scored ahead of the search included. */
 int gaml_hip_gap_profile(gaml_hip_ctx* ctx, const int32_t* paths, const int64_t* path_offs, int32_t n_paths,
                          int32_t path_id, int32_t gap_pos, const int32_t* lens, int32_t n_lens,
                          double* probs_out, int32_t* zeros_out /* n_lens * 2 * num_readsets, may be NULL */,
@@ -406,6 +417,8 @@ int gaml_hip_fix_gap_length(gaml_hip_ctx* ctx, const int32_t* paths, const int64
 int gaml_hip_gap_stats(gaml_hip_ctx* ctx, int64_t* out4);
 int gaml_hip_set_gap_penalty_device(gaml_hip_ctx* ctx, int32_t on);
 int gaml_hip_get_gap_penalty_device(const gaml_hip_ctx* ctx);
+int gaml_hip_set_gap_mixed_device(gaml_hip_ctx* ctx, int32_t on);
+int gaml_hip_get_gap_mixed_device(const gaml_hip_ctx* ctx);
 
 /* ---- introspection (tests, bench, logging) ----------------------------------------- */
 int gaml_hip_num_readsets(const gaml_hip_ctx* ctx);
@@ -450,7 +463,9 @@ int gaml_hip_table_stats(gaml_hip_ctx* ctx, int readset, int64_t* out10);
 /* record cache of a PacBio set: {cached sub-walks, cached records (this shard's reads), sub-walk lookups of the evaluations
  * so far that found nothing cached (cumulative; the reference would run BLASR there), gaml_hip_calc_prob_batch chunks the
  * set scored in one multi-set launch}. Host-only contexts too; GAML_HIP_EINVAL for a handle that is not a PacBio set. A
- * multi-device context reports its first shard, like gaml_hip_table_stats. */
+ * multi-device context reports its first shard, like gaml_hip_table_stats. A gap profile on the mixed device route
+ * (gaml_hip_set_gap_mixed_device) counts a pass as one such launch, and the lookups of every length a pass scored --
+ * those scored ahead of the search included, which the fallback never scores. */
 int gaml_hip_pacbio_stats(gaml_hip_ctx* ctx, int readset, int64_t* out4);
 /* a single-end set: {windows registered, records in the read-major table (those of the windows some scored path set has
  * named; this shard's reads), bytes of occurrence tables staged by the last call or chunk, gaml_hip_calc_prob_batch chunks

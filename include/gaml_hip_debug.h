@@ -63,6 +63,23 @@ int32_t gaml_hip_debug_cov_layout(gaml_hip_ctx* ctx, int readset, int32_t* slot_
  * the next evaluation re-uses the arena slot. */
 int32_t gaml_hip_debug_gap_cov_layout(gaml_hip_ctx* ctx, int readset, int g, int32_t* slot_base, int32_t cap_slots, int32_t* path_base,
                                       int32_t* start_off, int32_t* slots, int32_t cap_paths, int32_t* starts, int32_t cap_starts, int32_t* counts4);
+/* Region g of the last pass of a gap profile that took the mixed device route (gaml_hip_set_gap_mixed_device on), of single-end
+ * set `readset`: what gap_single_tables_kernel derived for the g-th length of that pass, copied back from the set's arena and
+ * listed like gaml_hip_debug_occurrences: 5 ints per entry {window id, shift, min_pos, path, rank}, by rank. Returns the number
+ * of entries, -1 when no such pass ran, the pass had no region g, or the context has no device. Call it before the next
+ * evaluation re-uses the arena. */
+int64_t gaml_hip_debug_gap_single_table(gaml_hip_ctx* ctx, int readset, int g, int32_t* out5, int64_t cap);
+/* Column g (0..7) of the count table [sub-walk][8] that gap_pacbio_counts_kernel built for the last such pass of PacBio set
+ * `readset`: out[w] = occurrences of cached sub-walk w in the path set with the pass's g-th length; columns behind the pass's
+ * lengths hold 0. Returns the number of sub-walks, -1 when no such pass ran or the context has no device. */
+int64_t gaml_hip_debug_gap_pacbio_counts(gaml_hip_ctx* ctx, int readset, int g, int32_t* out, int64_t cap);
+/* The split enumeration of that route for `path` (one path, entry gap_pos a gap) with `len` in the gap: what the lengths
+ * share + the growths that reach the gap, put together in the reference's order as {sub-walk id, begin} pairs (hits_out: 2
+ * ints per hit, at most cap hits written), *misses_out (may be NULL) the lookups that found nothing. Returns the number of
+ * hits; -1 on bad arguments, -2 when the result differs from the whole enumeration of the path (gaml_hip_last_error). Works
+ * on a host-only context. */
+int64_t gaml_hip_debug_pacbio_gap_enum(gaml_hip_ctx* ctx, int readset, const int32_t* path, int32_t path_len, int32_t gap_pos, int32_t len,
+                                       int32_t* hits_out, int64_t cap, int64_t* misses_out);
 /* node ids of a cached window (by id); returns its length, -1 if the id is unknown */
 int32_t gaml_hip_debug_window_walk(gaml_hip_ctx* ctx, int readset, int mate, int32_t window_id, int32_t* out, int32_t cap);
 /* ---- tuning ------------------------------------------------------------------------------------- */
